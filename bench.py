@@ -2,8 +2,16 @@
 """Throughput of the FoundationStereo hot path on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--with-backbone]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the headline line (pairs/s,
+``ms_per_step``).  ``--dump-outputs DIR`` also writes what the last timed step returned
+(``DIR/disparity.npy``; the inputs are seeded, so two builds can be compared output for output).
+``--full`` adds everything that takes work of its own after the timed region: the per-kernel
+rooflines (an eager timing pass, back-to-back replays), the CPU oracle baseline and the parity
+of the timed step's output against it.
 
 A step = one ``FoundationStereo.forward(test_mode=True)`` over this rank's
 pairs: cost-volume build, 3D filtering, context net, geometry encoding, 32
@@ -15,10 +23,10 @@ Multi-GPU: rank 0 scatters each rank its shard of the image batch every step
 and the disparities are all-gathered back (RCCL over xGMI), weights broadcast
 once.
 
-Rank 0 prints ONE JSON line.  ``roofline`` is the dominant HBM-bound kernel
-(the per-iteration geometry lookup), timed with HIP events on its launch
-stream over the timed region; ``cpu_baseline`` is the CPU oracle run on the
-host cores for one pair of the same workload (N=1, rank 0 only).
+Rank 0 prints ONE JSON line.  With ``--full``: ``roofline`` is the dominant
+HBM-bound kernel (the per-iteration geometry lookup), timed with HIP events on
+its launch stream over the timed region; ``cpu_baseline`` is the CPU oracle run
+on the host cores for one pair of the same workload (N=1, rank 0 only).
 """
 from __future__ import annotations
 
@@ -245,7 +253,13 @@ def main():
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--corr-levels", type=int, default=4)
     ap.add_argument("--pairs-per-gpu", type=int, default=0, help="override the config's pairs per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's disparities to DIR/disparity.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the per-kernel rooflines, the CPU oracle baseline "
+                         "and the output's parity against it (a plain run prints the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full at one GPU: skip the CPU oracle run (and with it the parity block)")
     ap.add_argument("--cudnn-benchmark", type=int, default=int(os.environ.get("FSMI_CUDNN_BENCHMARK", "0")),
                     help="MIOpen Find (exhaustive, slow first call) instead of immediate-mode heuristics")
     ap.add_argument("--mixed-precision", action="store_true",
@@ -269,6 +283,8 @@ def main():
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus, sys.argv[1:]))
     if a.dist_selftest:
@@ -338,7 +354,9 @@ def main():
     if a.graph:
         # the captured lookups carry the in-kernel clock (timer mode 2): after the timed replays their
         # stamps hold the last replay's launches, i.e. the lookup as it runs inside the timed step,
-        # beside the other streams' convs (what rocprof's per-launch average of this command sees)
+        # beside the other streams' convs (what rocprof's per-launch average of this command sees).
+        # A plain run captures them too, so that it times the very step a --full run does; only
+        # --full reads the stamps
         step_clock = os.environ.get("FSMI_BENCH_STEP_CLOCK", "1") != "0"
         if step_clock:
             ops.timer_enable(True, in_capture=True)
@@ -368,11 +386,97 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
-    # the timed replays' range flag, read before anything else runs: the eager timing pass below
+    # the timed replays' range flag, read before anything else runs: --full's eager timing pass
     # goes through ops.guarded, which resets the flag.  A replay that overflowed also NaN-fills its
     # output (the captured forward's last node, ops.range_poison_); both are reported
     range_overflow = ops.range_overflowed(reset=False)
     out_finite = bool(torch.isfinite(out).all())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)       # before --full runs anything else on the device
+    if a.full:
+        extra = full_figures(a, runner, step, out, args, rank, world, elapsed, sizes, (lo, hi), B)
+    else:
+        ops.timer_enable(False)                 # --graph 0 times its steps with the kernel timers on
+        extra = {}
+    res = {
+        "metric": f"stereo pairs/sec ({iters} refinement iters)",
+        "value": a.steps * B / elapsed,
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "world_size": wsz,            # torch.distributed's view (1 without a process group)
+        "backend": backend,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * elapsed / a.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        # fp32 arithmetic throughout; the convs run as 3 fp16 MFMA products per MAC on fp16 hi/lo
+        # splits (~22-bit operand mantissas, fp32 accumulation), not as fp32 MFMA
+        "dtype": ("fp16 convs (1 fp16 MFMA product per MAC, fp32 accumulate; fp32 volumes + lookup)"
+                  if a.precision == "fast" else
+                  "f32 (3xfp16 split MFMA convs; library convs fp16 under autocast)" if a.mixed_precision
+                  else "f32 (3xfp16 split MFMA)"),
+        "precision": a.precision,
+        "full": bool(a.full),
+        "data": ("synthetic (hash-PRNG images, hash-init weights incl. the backbone)" if a.with_backbone else
+                 "synthetic (hash-PRNG images + synthetic backbone features, hash-init weights)"),
+        "range_overflow": range_overflow,             # set during the timed replays
+        "output_finite": out_finite,
+        # forwards re-run in safe range mode after their range flag came back set (ops.guarded)
+        "range_recoveries": ops.RANGE_RECOVERIES[0],
+        # HBM high-water mark of this rank's process (caching allocator: tensors, workspaces, the captured
+        # graph's private pool) -- the 288 GB budget the per-GPU batch is sized against
+        "peak_mem_gb": round(torch.cuda.max_memory_allocated(device) / 1e9, 3),
+        "config": {"workload": f"{a.config}: {W}x{H}{' hierarchical' if a.config in HIERA else ''}, "
+                               f"max_disp {md}, {iters} iters, {vit}, "
+                               f"corr_levels {L}, {per_gpu} pair(s)/GPU; forward "
+                               + ("INCL. backbone (Feature on HIP; secondary line)" if a.with_backbone
+                                  else "excl. backbone"),
+                   "backbone": "real" if a.with_backbone else "preset features (excluded)",
+                   "global_batch": B, "resolution": f"{W}x{H}", "max_disp": md, "iters": iters,
+                   "corr_levels": L, "conv_engine": a.conv_engine, "hip_graph": bool(a.graph),
+                   "parallelism": f"dp{world}"},
+        # N > 1: each rank's own step time and its scatter / forward / all-gather split (max over ranks
+        # is `ms_per_step`); the world size every rank's process group reported
+        **({"rank_attribution": attribution} if attribution else {}),
+        **extra,
+    }
+    if rank == 0:
+        # a multi-GPU --full line never prints without parity (its pairs came back through the all-gather)
+        assert not a.full or world == 1 or "max_abs_dd_px" in res.get("parity", {}), "multi-GPU line without parity"
+        print(json.dumps(res), flush=True)
+    if not out_finite:
+        raise SystemExit("bench.py: the timed step returned non-finite disparities (range overflow)")
+    if torch.distributed.is_initialized():
+        torch.distributed.destroy_process_group()
+
+
+DUMP_LIMIT = 60 * 10**6     # bytes of array data --dump-outputs may write (files stay under 64 MB)
+
+
+def dump_outputs(path, out):
+    """``--dump-outputs``: the disparities the last timed step returned (the gathered batch,
+    (B, 1, H, W)) as ``path/disparity.npy`` in float32 -- whole, or beyond DUMP_LIMIT a fixed
+    seeded sample of its elements (the same indices every run: they depend on the size alone)."""
+    disp = out.detach().float().cpu().numpy()
+    if disp.nbytes > DUMP_LIMIT:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(disp.size, DUMP_LIMIT // 8, replace=False))
+        disp = disp.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "disparity.npy"), np.ascontiguousarray(disp, dtype=np.float32))
+
+
+def full_figures(a, runner, step, out, args, rank, world, elapsed, sizes, shard, B):
+    """``--full``: what the line holds beyond the headline, measured after the timed region -- the
+    kernels' clocks of the last timed step, one eager timing pass of the identical step, back-to-back
+    replays of the build launch, and the CPU oracle (baseline and parity of ``out``)."""
+    from foundationstereo_amd import ops
+    from foundationstereo_amd import update as fupdate
+    H, W, md, iters, vit, per_gpu = CONFIGS[a.config]
+    per_gpu = a.pairs_per_gpu or per_gpu
+    L = a.corr_levels
+    lo, hi = shard
     # the timed step's own launches (the last replay), by the kernels' clocks baked into the graph
     in_step = {k: ops.timer_query_clock(k, captured=True) for k in GEO_KERNELS} if a.graph else {}
     lk_step_ms, lk_step_n = in_step.get("lookup", (0.0, 0))
@@ -453,54 +557,13 @@ def main():
             traffic = pmc.get("hbm_bytes_per_launch")
             traffic_build = pmc.get("build_hbm_bytes_per_launch")
 
-    pairs = a.steps * B
     nprod = 1 if a.precision == "fast" else 3      # fp16 MFMA products per conv MAC
     res = {
-        "metric": f"stereo pairs/sec ({iters} refinement iters)",
-        "value": pairs / elapsed,
-        "unit": "pairs/s",
-        "n_gpus": world,
-        "world_size": wsz,            # torch.distributed's view (1 without a process group)
-        "backend": backend,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": 1e3 * elapsed / a.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        # fp32 arithmetic throughout; the convs run as 3 fp16 MFMA products per MAC on fp16 hi/lo
-        # splits (~22-bit operand mantissas, fp32 accumulation), not as fp32 MFMA
-        "dtype": ("fp16 convs (1 fp16 MFMA product per MAC, fp32 accumulate; fp32 volumes + lookup)"
-                  if a.precision == "fast" else
-                  "f32 (3xfp16 split MFMA convs; library convs fp16 under autocast)" if a.mixed_precision
-                  else "f32 (3xfp16 split MFMA)"),
-        "precision": a.precision,
-        "data": ("synthetic (hash-PRNG images, hash-init weights incl. the backbone)" if a.with_backbone else
-                 "synthetic (hash-PRNG images + synthetic backbone features, hash-init weights)"),
-        "range_overflow": range_overflow,             # set during the timed replays
         "range_overflow_timing_pass": range_overflow_eager,
-        "output_finite": out_finite,
-        # forwards re-run in safe range mode after their range flag came back set (ops.guarded)
-        "range_recoveries": ops.RANGE_RECOVERIES[0],
-        # HBM high-water mark of this rank's process (caching allocator: tensors, workspaces, the captured
-        # graph's private pool) -- the 288 GB budget the per-GPU batch is sized against
-        "peak_mem_gb": round(torch.cuda.max_memory_allocated(device) / 1e9, 3),
-        "config": {"workload": f"{a.config}: {W}x{H}{' hierarchical' if a.config in HIERA else ''}, "
-                               f"max_disp {md}, {iters} iters, {vit}, "
-                               f"corr_levels {L}, {per_gpu} pair(s)/GPU; forward "
-                               + ("INCL. backbone (Feature on HIP; secondary line)" if a.with_backbone
-                                  else "excl. backbone"),
-                   "backbone": "real" if a.with_backbone else "preset features (excluded)",
-                   "global_batch": B, "resolution": f"{W}x{H}", "max_disp": md, "iters": iters,
-                   "corr_levels": L, "conv_engine": a.conv_engine, "hip_graph": bool(a.graph),
-                   "parallelism": f"dp{world}"},
         # headline: the lookup as it runs INSIDE the timed step (its in-kernel clock, first wave start
         # to last wave end, baked into the captured graph: the last timed replay's launches, beside the
         # other streams' kernels that share the chip and its HBM); the single-stream eager pass after
         # the timed region is kept as a secondary figure
-        # N > 1: each rank's own step time and its scatter / forward / all-gather split (max over ranks
-        # is `ms_per_step`); the world size every rank's process group reported
-        **({"rank_attribution": attribution} if attribution else {}),
         "roofline": {"kernel": "geo_lookup", "bound": "hbm",
                      "timed_over": ("the timed step (last replay's launches)" if lk_head_in_step else
                                     "single-stream eager step after the timed region" if a.graph else "timed region"),
@@ -580,14 +643,7 @@ def main():
                                "sample": f"1 pair of {a.config} (all {iters} iterations) through the fp32 "
                                          f"torch-CPU oracle, {dt:.1f} s",
                                "stages_s": {k: round(v, 3) for k, v in stages.items()}}
-    if rank == 0:
-        # a multi-GPU line never prints without parity (its pairs came back through the all-gather)
-        assert world == 1 or "max_abs_dd_px" in res.get("parity", {}), "multi-GPU line without parity"
-        print(json.dumps(res), flush=True)
-    if not out_finite:
-        raise SystemExit("bench.py: the timed step returned non-finite disparities (range overflow)")
-    if torch.distributed.is_initialized():
-        torch.distributed.destroy_process_group()
+    return res
 
 
 if __name__ == "__main__":

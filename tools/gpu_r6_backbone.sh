@@ -6,4 +6,5 @@ rc=$?
 echo "backbone tests rc=$rc" >> gpurun_out/r6_backbone_tests.txt
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -u __graft_entry__.py smoke > gpurun_out/r6_smoke.txt 2>&1 || exit $?
-timeout -k 10 600 python -u bench.py --with-backbone --steps 5 --warmup 2 > gpurun_out/r6_cfg2_backbone_bench.json 2> gpurun_out/r6_cfg2_backbone_bench.err
+O=${GPU_OUT:-bench_out}; mkdir -p $O
+timeout -k 10 600 python -u bench.py --full --with-backbone --steps 5 --warmup 2 > $O/r6_cfg2_backbone_bench.json 2> $O/r6_cfg2_backbone_bench.err

@@ -9,7 +9,7 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -q --timeout 400 --timeout-me
 rc=$?; echo "gpu tests rc=$rc" >> $O/gpu_tests.txt
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -u __graft_entry__.py smoke > $O/smoke.txt 2>&1 || exit $?
-timeout -k 10 400 python -u bench.py > $O/cfg2_bench.json 2> $O/cfg2_bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full > $O/cfg2_bench.json 2> $O/cfg2_bench.err || exit $?
 cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/prof -o cfg2 -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/cfg2_under_rocprof.json 2> $GRAFT_REPO_ROOT/$O/cfg2_under_rocprof.err
 rc=$?; echo "rocprof rc=$rc" >> $GRAFT_REPO_ROOT/$O/cfg2_under_rocprof.err
 [ $rc -eq 0 ] || exit $rc

@@ -33,14 +33,14 @@ for step in "$@"; do
       tail -2 $OUT/smoke.log ;;
     bench|bench3|bench4|bench5)
       cfg=cfg2; [ $step = bench3 ] && cfg=cfg3; [ $step = bench4 ] && cfg=cfg4; [ $step = bench5 ] && cfg=cfg5
-      timeout -k 10 400 python3 bench.py --config $cfg --steps ${STEPS:-20} --warmup 5 $BENCH_ARGS \
+      timeout -k 10 400 python3 bench.py --full --config $cfg --steps ${STEPS:-20} --warmup 5 $BENCH_ARGS \
         > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || fail bench $? $OUT/bench_$cfg.err
       python3 tools/bench_brief.py $OUT/bench_$cfg.json ;;
     trace|trace3)
       cfg=cfg2; [ $step = trace3 ] && cfg=cfg3
       rm -rf $OUT/trace_$cfg
       timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$cfg -o run -- \
-        python3 bench.py --config $cfg --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline $BENCH_ARGS \
+        python3 bench.py --full --config $cfg --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline $BENCH_ARGS \
         > $OUT/trace_bench_$cfg.json 2> $OUT/trace_$cfg.err || fail trace $? $OUT/trace_$cfg.err
       python3 tools/bench_brief.py $OUT/trace_bench_$cfg.json
       python3 tools/stats_brief.py $OUT/trace_$cfg --top 25 > $OUT/trace_$cfg.txt && head -40 $OUT/trace_$cfg.txt ;;
