@@ -3,7 +3,8 @@
 Hand-written gfx950 HIP kernels (``csrc/``, C ABI in ``include/fsmi.h``,
 loaded via ctypes from ``_lib/libfsmi.so``) behind the reference's own module
 and function API (``submodule``, ``geometry``, ``update``, ``utils``,
-``foundation_stereo``, and the backbone ``backbone.Feature``).  See DESIGN.md.
+``foundation_stereo``, and the backbone ``backbone.Feature``), plus ``cloud``:
+depth, XYZ map and denoised point cloud from the disparity.  See DESIGN.md.
 """
 import os as _os
 

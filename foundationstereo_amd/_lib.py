@@ -69,6 +69,9 @@ SIGNATURES = {
     "fsmi_dt_patch_embed": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "fsmi_disparity_transformer": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "fsmi_upsample4_add": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "fsmi_disp_to_xyz": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P],
+    "fsmi_cloud_cell_keys": [_P, _P, _P, _I, _F, _P],
+    "fsmi_radius_count": [_P, _P, _P, _P, _I, _F, _I, _P],
     "fsmi_debug_conv_timestamps": [_P],
     "fsmi_range_status": [_I, ctypes.POINTER(_I)],
     "fsmi_set_range_safe": [_I],

@@ -11,12 +11,16 @@
 //   geo_lookup          core/geometry.py:43-65         bilinear_sampler  core/utils/utils.py:44-55
 //   disparity_regression core/submodule.py:431-435     softmax_regression core/foundation_stereo.py:218-220
 //   context_upsample    core/submodule.py:456-468      softmax_context_upsample core/foundation_stereo.py:187-189
+//   disp_to_xyz         scripts/run_demo.py:173-251, Utils.py:56-75
+//   radius_outlier_mask scripts/run_demo.py:270-273 (Open3D remove_radius_outlier)
 #include <torch/library.h>
 #include <ATen/core/Tensor.h>
 #include <ATen/ops/empty.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cstdint>
+#include <tuple>
 #include <vector>
 
 #include "../../include/fsmi.h"
@@ -204,6 +208,56 @@ Tensor softmax_context_upsample(const Tensor& disp_, const Tensor& logits_, doub
   return out;
 }
 
+std::tuple<Tensor, Tensor, Tensor> disp_to_xyz(const Tensor& disp_, double fx, double fy, double cx, double cy,
+                                               double baseline, double zmin, double z_far, bool remove_invisible,
+                                               int64_t camera_type) {
+  const c10::DeviceGuard guard(disp_.device());
+  check_dev("disp_to_xyz", disp_);
+  TORCH_CHECK(disp_.dim() == 3, "disp_to_xyz: disp must be (B,H,W)");
+  Tensor disp = dense(disp_);
+  const int64_t B = disp.size(0), H = disp.size(1), W = disp.size(2);
+  Tensor xyz = at::empty({B, H, W, 3}, disp.options());
+  Tensor depth = at::empty({B, H, W}, disp.options());
+  Tensor valid = at::empty({B, H, W}, disp.options().dtype(at::kByte));
+  ok(fsmi_disp_to_xyz(cp(disp), mp(xyz), mp(depth), valid.data_ptr<uint8_t>(), B, H, W, (float)fx, (float)fy,
+                      (float)cx, (float)cy, (float)baseline, (float)zmin, (float)z_far, remove_invisible ? 1 : 0,
+                      (int)camera_type, stream_of(disp)),
+     "disp_to_xyz");
+  return {xyz, depth, valid.view(at::kBool)};
+}
+
+// keys -> sort -> gather -> count, the sequence of ops.radius_outlier_mask on the current stream
+Tensor radius_outlier_mask(const Tensor& points_, const c10::optional<Tensor>& valid_, int64_t nb_points,
+                           double radius) {
+  const c10::DeviceGuard guard(points_.device());
+  check_dev("radius_outlier_mask", points_);
+  TORCH_CHECK(points_.dim() == 2 && points_.size(1) == 3, "radius_outlier_mask: points must be (N,3)");
+  Tensor points = dense(points_);
+  const int64_t N = points.size(0);
+  TORCH_CHECK(N <= INT32_MAX, "radius_outlier_mask: N exceeds 2^31 - 1");
+  Tensor valid;
+  if (valid_.has_value() && valid_->defined()) {
+    TORCH_CHECK(valid_->device() == points.device() && valid_->numel() == N &&
+                    (valid_->scalar_type() == at::kBool || valid_->scalar_type() == at::kByte),
+                "radius_outlier_mask: valid must hold N bool / uint8 values on the device of points");
+    valid = valid_->reshape({N}).contiguous().view(at::kByte);
+  }
+  void* s = stream_of(points);
+  Tensor keys = at::empty({N}, points.options().dtype(at::kLong));
+  ok(fsmi_cloud_cell_keys(cp(points), valid.defined() ? valid.data_ptr<uint8_t>() : nullptr,
+                          reinterpret_cast<long long*>(keys.data_ptr<int64_t>()), (int)N, (float)radius, s),
+     "cloud_cell_keys");
+  auto [skeys, perm] = keys.sort();
+  Tensor pts4 = at::empty({N, 4}, points.options()).zero_();
+  pts4.narrow(1, 0, 3).copy_(points.index_select(0, perm));
+  Tensor keep = at::empty({N}, points.options().dtype(at::kByte));
+  ok(fsmi_radius_count(reinterpret_cast<const long long*>(skeys.data_ptr<int64_t>()),
+                       reinterpret_cast<const long long*>(perm.data_ptr<int64_t>()), cp(pts4),
+                       keep.data_ptr<uint8_t>(), (int)N, (float)radius, (int)nb_points, s),
+     "radius_count");
+  return keep.view(at::kBool);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(fsmi, m) {
@@ -218,6 +272,10 @@ TORCH_LIBRARY(fsmi, m) {
   m.def("softmax_regression(Tensor logits) -> Tensor");
   m.def("context_upsample(Tensor disp_low, Tensor up_weights) -> Tensor");
   m.def("softmax_context_upsample(Tensor disp_low, Tensor logits, float scale=4.0) -> Tensor");
+  // after the forward (scripts/run_demo.py:173-275): camera_type 0 pinhole, 1 panorama
+  m.def("disp_to_xyz(Tensor disp, float fx, float fy, float cx, float cy, float baseline, float zmin=0.1, "
+        "float z_far=10.0, bool remove_invisible=True, int camera_type=0) -> (Tensor, Tensor, Tensor)");
+  m.def("radius_outlier_mask(Tensor points, Tensor? valid=None, int nb_points=30, float radius=0.03) -> Tensor");
 }
 
 // ROCm builds of PyTorch expose HIP devices under the CUDA dispatch key
@@ -232,4 +290,6 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("softmax_regression", softmax_regression);
   m.impl("context_upsample", context_upsample);
   m.impl("softmax_context_upsample", softmax_context_upsample);
+  m.impl("disp_to_xyz", disp_to_xyz);
+  m.impl("radius_outlier_mask", radius_outlier_mask);
 }

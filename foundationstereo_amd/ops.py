@@ -1201,3 +1201,57 @@ def dwconv2d_ex(x, w: Tensor, bias: Tensor = None, add=None, out=None) -> Tensor
         at.shape[1] if add is not None else C, _p(w), _p(b) if b is not None else None, _p(ot) + 4 * oc0 * HW,
         ot.shape[1], B, C, KS, H, W, _stream(xt)), "dwconv2d_ex")
     return ot
+
+
+# ---------------------------------------------------------------- point cloud
+
+CAMERA_TYPES = {"pinhole": 0, "panorama": 1}
+
+
+def disp_to_xyz(disp: Tensor, fx: float, fy: float, cx: float, cy: float, baseline: float, zmin: float = 0.1,
+                z_far: float = 10.0, remove_invisible: bool = True, camera_type: str = "pinhole"):
+    """scripts/run_demo.py:173-251 + Utils.py:56-75.  disp (B,H,W) -> xyz (B,H,W,3) fp32, depth (B,H,W)
+    fp32, valid (B,H,W) bool; one camera for the whole batch (include/fsmi.h for the semantics)."""
+    if camera_type not in CAMERA_TYPES:
+        raise ValueError(f"disp_to_xyz: camera_type {camera_type!r}: 'pinhole' or 'panorama'")
+    _check("disp_to_xyz", disp)
+    assert disp.dim() == 3, f"disp_to_xyz: disp must be (B,H,W), got {tuple(disp.shape)}"
+    B, H, W = disp.shape
+    disp = _c(disp)
+    xyz = torch.empty((B, H, W, 3), device=disp.device, dtype=torch.float32)
+    depth = torch.empty((B, H, W), device=disp.device, dtype=torch.float32)
+    valid = torch.empty((B, H, W), device=disp.device, dtype=torch.uint8)
+    _lib.check(_lib.load().fsmi_disp_to_xyz(_p(disp), _p(xyz), _p(depth), _p(valid), B, H, W, float(fx), float(fy),
+                                            float(cx), float(cy), float(baseline), float(zmin), float(z_far),
+                                            int(bool(remove_invisible)), CAMERA_TYPES[camera_type], _stream(disp)),
+               "disp_to_xyz")
+    return xyz, depth, valid.view(torch.bool)
+
+
+def radius_outlier_mask(points: Tensor, valid: Tensor = None, nb_points: int = 30, radius: float = 0.03) -> Tensor:
+    """Open3D's remove_radius_outlier (scripts/run_demo.py:272) as a mask: points (N,3), valid (N) bool
+    or uint8 -> keep (N) bool, true where more than ``nb_points`` valid points (the point itself
+    included) lie closer than ``radius``.  Masked-out and non-finite points are neither counted nor
+    kept.  Keys, torch.sort, the gather and the count all queue on the current stream."""
+    _check("radius_outlier_mask", points)
+    assert points.dim() == 2 and points.shape[1] == 3, f"radius_outlier_mask: points must be (N,3), got {tuple(points.shape)}"
+    N = points.shape[0]
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.device != points.device:
+            raise RuntimeError("radius_outlier_mask: valid must be a tensor on the device of points")
+        if valid.dtype not in (torch.bool, torch.uint8) or valid.numel() != N:
+            raise RuntimeError(f"radius_outlier_mask: valid must hold {N} bool / uint8 values")
+        valid = valid.reshape(N).contiguous().view(torch.uint8)
+    lib = _lib.load()
+    points = _c(points)
+    s = _stream(points)
+    keys = torch.empty((N,), device=points.device, dtype=torch.int64)
+    _lib.check(lib.fsmi_cloud_cell_keys(_p(points), _p(valid) if valid is not None else None, _p(keys), N,
+                                        float(radius), s), "cloud_cell_keys")
+    skeys, perm = torch.sort(keys)
+    pts4 = torch.zeros((N, 4), device=points.device, dtype=torch.float32)
+    pts4[:, :3] = points.index_select(0, perm)
+    keep = torch.empty((N,), device=points.device, dtype=torch.uint8)
+    _lib.check(lib.fsmi_radius_count(_p(skeys), _p(perm), _p(pts4), _p(keep), N, float(radius), int(nb_points), s),
+               "radius_count")
+    return keep.view(torch.bool)

@@ -23,7 +23,8 @@ _BUILD_DIR = os.path.join(os.path.dirname(PKG), "build", "fsmi_torch")
 _loaded = False
 
 OPS = ("gwc_volume", "concat_volume", "allpairs_corr", "volume_pyramid", "geo_lookup", "bilinear_sampler_1d",
-       "disparity_regression", "softmax_regression", "context_upsample", "softmax_context_upsample")
+       "disparity_regression", "softmax_regression", "context_upsample", "softmax_context_upsample",
+       "disp_to_xyz", "radius_outlier_mask")
 
 
 def build_extension(force: bool = False, verbose: bool = False) -> str:

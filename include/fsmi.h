@@ -369,6 +369,48 @@ long long fsmi_xca_workspace_floats(int B, int C, int heads);
 int fsmi_dwconv2d_ex(const float* x, int x_ctot, const float* add, int add_ctot, const float* w, const float* bias,
                      float* out, int out_ctot, int B, int C, int KS, int H, int W, void* stream);
 
+/* ---- after the forward: depth, XYZ map and cloud denoising ---------------
+ * The three entry points below take, next to fp32 tensors, a uint8 mask and int64 keys / indices
+ * (the one exception to the all-fp32 convention above).
+ *
+ * Disparity to metric depth and an XYZ map; replaces scripts/run_demo.py:173-251 and
+ * depth2xyzmap, Utils.py:56-75.  disp: (B,H,W); xyz: (B,H,W,3); depth: (B,H,W); valid: (B,H,W)
+ * uint8.  disp, xyz and depth must be 16-byte aligned, valid 4-byte aligned; B*H*W < 2^31.  One
+ * camera serves the whole batch.  For pixel (u = column, v = row):
+ *   removed = remove_invisible and u - disp < 0          (run_demo.py:174-178)
+ * FSMI_CAMERA_PINHOLE:
+ *   depth = fx * baseline / disp, 0 where removed        (run_demo.py:235)
+ *   xyz   = ((u-cx) z / fx, (v-cy) z / fy, z), zero where depth < zmin or depth is not finite
+ *   valid = not removed, disp finite, 0 < z <= z_far, with z the (zeroed) third component of xyz
+ * FSMI_CAMERA_PANORAMA (up/down equirectangular rig, run_demo.py:186-219; fx, fy, cx, cy, zmin and
+ * z_far are unused):
+ *   lon_up = (2v/H - 1) pi, lat_up = (2u/W - 1) pi/2, lat_down = (2(u-disp)/W - 1) pi/2,
+ *   tr = baseline cos(lat_down) / sin(2 pi disp / W), 0 where removed;  depth = tr
+ *   xyz = tr (sin lat_up, -cos lat_up cos lon_up, cos lat_up sin lon_up), zero where tr is not finite
+ *   valid = not removed, tr finite and positive
+ * xyz never holds NaN or inf; depth holds the raw quotient (inf for disp = 0, NaN for NaN). */
+#define FSMI_CAMERA_PINHOLE 0
+#define FSMI_CAMERA_PANORAMA 1
+int fsmi_disp_to_xyz(const float* disp, float* xyz, float* depth, unsigned char* valid, int B, int H, int W,
+                     float fx, float fy, float cx, float cy, float baseline, float zmin, float z_far,
+                     int remove_invisible, int camera_type, void* stream);
+/* Radius outlier removal (scripts/run_demo.py:270-273, Open3D's remove_radius_outlier) on a uniform
+ * grid of cell = radius (1 + 2^-20): points closer than radius are at most one cell apart per axis.
+ * Step 1, one int64 key per slot.  points: (N,3); valid: (N) uint8 or NULL; keys: (N) int64.
+ *   index = clamp(floor(coord / cell), +-(2^20 - 1)) + 2^20 - 1 per axis,
+ *   key = ix << 42 | iy << 21 | iz;  INT64_MAX for a slot that is masked out or not finite.
+ * The caller sorts the keys ascending (any sort; ties in any order) and gathers the points in that
+ * order into rows of 4 floats (x, y, z, unused). */
+int fsmi_cloud_cell_keys(const float* points, const unsigned char* valid, long long* keys, int N, float radius,
+                         void* stream);
+/* Step 2.  sorted_keys: (N) int64 ascending; perm: (N) int64, the slot each sorted row came from;
+ * sorted_points4: (N,4), 16-byte aligned; keep: (N) uint8, every slot written.  Each valid point
+ * counts the points (itself included) with squared fp32 distance < radius^2 among the 27 cells
+ * around its own, stopping once the count exceeds nb_points:  keep[perm[i]] = count > nb_points,
+ * 0 for INT64_MAX keys.  N = 0 succeeds and launches nothing (both steps). */
+int fsmi_radius_count(const long long* sorted_keys, const long long* perm, const float* sorted_points4,
+                      unsigned char* keep, int N, float radius, int nb_points, void* stream);
+
 /* ---- live kernel timing (bench.py roofline) -----------------------------
  * When enabled, every launch of the kernels below is bracketed by a pair of
  * hipEvents recorded on the launch stream (skipped while the stream is being

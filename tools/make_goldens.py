@@ -246,10 +246,39 @@ def backbone():
             json.dump([[k, list(v.shape)] for k, v in m.state_dict().items()], f)
 
 
+CLOUD_CASES = {"a": (5, 7), "b": (33, 70)}
+
+
+def cloud():
+    """depth2xyzmap (Utils.py:56-75) run by the reference on two small depth maps that include zeros
+    and pixels below zmin: pins tests/cloud_oracle.py.  The rest of the demo's cloud code sits under
+    ``if __name__ == "__main__"`` (scripts/run_demo.py) and cannot be called."""
+    import_reference()          # installs the stubs Utils.py's imports need
+    import importlib
+    ref_utils = importlib.import_module("Utils")
+    K = np.array([[61.5, 0.0, 33.25], [0.0, 59.75, 15.5], [0.0, 0.0, 1.0]], dtype=np.float32)
+    g = {"K": K, "zmin": np.float32(0.1)}
+    for tag, (H, W) in CLOUD_CASES.items():
+        depth = synth.uniform(synth.name_seed(f"cloud_depth_{tag}"), (H, W), 0.02, 6.0).astype(np.float32)
+        depth[0, 0] = 0.0
+        depth[H // 2, W // 3] = 0.0
+        depth[H - 1, W - 1] = 0.05                        # below zmin
+        depth[1, 2] = 0.0999
+        depth[2, 1] = 0.1001
+        g[f"depth_{tag}"] = depth
+        g[f"xyz_{tag}"] = ref_utils.depth2xyzmap(depth.copy(), K.copy(), zmin=0.1)
+    np.savez_compressed(os.path.join(OUT, "cloud_small.npz"), **g)
+    print("cloud_small", {k: (v.shape, v.dtype) for k, v in g.items()})
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud"]
+    if "cloud" in which:
+        cloud()
+    if which == ["cloud"]:
+        return
     fs, sm, geo_mod, up_mod, ut = import_reference()
-    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone"]
     if "backbone" in which:
         backbone()
     if "hiera" in which:
