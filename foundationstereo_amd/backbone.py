@@ -31,7 +31,7 @@ import torch.nn.functional as F
 from . import ops
 from . import submodule as _sub
 from .extractor import DepthAnythingFeature as _DAFConfig, ResidualBlock
-from .submodule import BasicConv, Conv2x_IN
+from .submodule import BasicConv, Conv2x_IN, _cached
 
 __all__ = ["DinoVisionTransformer", "vit_small", "vit_base", "vit_large", "DPTHead", "DepthAnything",
            "DepthAnythingFeature", "EdgeNeXt", "edgenext_small", "Feature", "get_resize_keep_aspect_ratio"]
@@ -42,17 +42,6 @@ def _need_hip(x, what):
         raise RuntimeError(f"{what}: the backbone runs on ROCm (HIP) device tensors only (CPU restatement: oracle/)")
     if torch.is_grad_enabled() and any(p.requires_grad for p in [x]):
         raise RuntimeError(f"{what}: inference-only (input requires grad)")
-
-
-def _cached(mod, name, tensors, build):
-    """``build()`` cached on ``mod`` until any tensor in ``tensors`` is replaced or modified."""
-    key = tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
-    hit = mod.__dict__.get(name)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, build())
-        mod.__dict__[name] = hit
-    return hit[1]
 
 
 def _bias(b, n, dev):

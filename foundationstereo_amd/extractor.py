@@ -1,11 +1,13 @@
 """Context network and the backbone seam (``core/extractor.py``).
 
-The context path runs once per pair before the refinement loop and is OUT of
-the hot-path scope: it stays stock PyTorch-ROCm here, with
-the reference's module tree so checkpoints load.  The backbone (EdgeNeXt-S +
-DepthAnythingV2, ``Feature``) needs remote weights and is out of scope
-(SURVEY §2 row 9); ``SyntheticFeature`` stands in for it, returning
-device-resident feature maps with ``Feature.d_out`` channels.
+The context path runs once per pair before the refinement loop, with the reference's module tree so
+checkpoints load.  Its convs run on the halo conv engine where ``submodule._route`` finds a tile for
+them (stride-1 1x1 / 3x3 and the stride-2 downsampling convs, eval BatchNorm folded into the packed
+weights, the residual add in the epilogue), its InstanceNorms on ``ops.instance_norm``; the 7x7 stem
+conv and anything run with grad or on the CPU stay on torch.  The backbone (EdgeNeXt-S +
+DepthAnythingV2, ``Feature``) lives in ``backbone.py``; ``SyntheticFeature`` stands in for it in the
+benchmark (backbone excluded there), returning device-resident feature maps with ``Feature.d_out``
+channels.
 """
 from __future__ import annotations
 
@@ -14,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops, synth
-from .submodule import BasicConv, _fast2d, _fast_s2_2d, _hip_in, conv2d_bn_act, conv2d_s2_bn_act
+from .submodule import BasicConv, _hip_in, _route, conv2d_bn_act, conv2d_s2_bn_act
 
 __all__ = ["ResidualBlock", "ContextNetDino", "DepthAnythingFeature", "SyntheticFeature"]
 
@@ -57,25 +59,25 @@ class ResidualBlock(nn.Module):
     def forward(self, x):
         n1 = self.norm1 if isinstance(self.norm1, nn.BatchNorm2d) else None
         n2 = self.norm2 if isinstance(self.norm2, nn.BatchNorm2d) else None
-        if n1 is not None and n2 is not None and _fast2d(x, self.conv2, n2):
+        if n1 is not None and n2 is not None and _route(x, self.conv2, n2) == "s1":
             # every conv on the halo kernel with the eval BN folded in: stride-1 convs as 2D maps,
             # a downsampling block's 3x3 s2 conv and 1x1 s2 projection on the stride-2 tiles, the
             # projection finishing the block: relu(bn3(proj(x)) + y) in its epilogue
-            if _fast2d(x, self.conv1, n1):
+            if _route(x, self.conv1, n1) == "s1":
                 y = conv2d_bn_act([x], self.conv1, n1, "relu")
-            elif _fast_s2_2d(x, self.conv1, n1):
+            elif _route(x, self.conv1, n1) == "s2":
                 y = conv2d_s2_bn_act(x, self.conv1, n1, "relu")
             else:
                 y = F.relu(n1(self.conv1(x)))
             y = conv2d_bn_act([y], self.conv2, n2, "relu")
             if self.downsample is not None:
                 pc, n3 = self.downsample
-                if isinstance(n3, nn.BatchNorm2d) and _fast_s2_2d(x, pc, n3):
+                if isinstance(n3, nn.BatchNorm2d) and _route(x, pc, n3) == "s2":
                     return conv2d_s2_bn_act(x, pc, n3, "relu", res=y, res_pre=True)
                 x = self.downsample(x)
             return torch.relu_(y.add_(x))
         if (self.downsample is None and _hip_in(self.norm1, x) and _hip_in(self.norm2, x)
-                and _fast2d(x, self.conv1, None) and _fast2d(x, self.conv2, None)):
+                and _route(x, self.conv1) == "s1" and _route(x, self.conv2) == "s1"):
             # norm_fn='instance' (Feature.conv4): relu(x + relu(IN(conv2(relu(IN(conv1 x))))))
             x = x.float()
             y = ops.instance_norm(conv2d_bn_act([x], self.conv1, None), act="relu", eps=self.norm1.eps)
@@ -91,9 +93,9 @@ class ResidualBlock(nn.Module):
 def _head(f, x):
     """Output head: [ResidualBlock,] Conv2d(3x3, bias); the conv on the halo kernel when it can."""
     if isinstance(f, nn.Conv2d):
-        return conv2d_bn_act([x], f, None) if _fast2d(x, f, None) else f(x)
+        return conv2d_bn_act([x], f, None) if _route(x, f) == "s1" else f(x)
     x = f[0](x)
-    return conv2d_bn_act([x], f[1], None) if _fast2d(x, f[1], None) else f[1](x)
+    return conv2d_bn_act([x], f[1], None) if _route(x, f[1]) == "s1" else f[1](x)
 
 
 class ContextNetDino(nn.Module):
@@ -135,7 +137,7 @@ class ContextNetDino(nn.Module):
     def forward(self, x_in, vit_feat, dual_inp=False, num_layers=3):
         x = self.relu1(self.norm1(self.conv1(x_in)))
         x = self.layer3(self.layer2(self.layer1(x)))
-        if _fast2d(x, self.conv2.conv, self.conv2.bn) and vit_feat.is_contiguous() and x.shape[1] % 8 == 0:
+        if _route(x, self.conv2.conv, self.conv2.bn) == "s1" and vit_feat.is_contiguous() and x.shape[1] % 8 == 0:
             x = conv2d_bn_act([x, vit_feat], self.conv2.conv, self.conv2.bn, "leaky")   # cat as segments
         else:
             x = self.conv2(torch.cat([x, vit_feat], dim=1))

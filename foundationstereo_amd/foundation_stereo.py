@@ -59,13 +59,12 @@ def normalize_image(img):
 _NORM_CACHE = {}
 
 
-# the context net (+ stem_2, CAM / SAM) and the hourglass's disparity-transformer branch on side
-# streams beside the 3D path (FSMI_CTX_OVERLAP=0: in order on the current stream, for A/B)
-CTX_OVERLAP = os.environ.get("FSMI_CTX_OVERLAP", "1") != "0"
-# range guard of the split-precision convs, enforced per eager forward (see forward); FSMI_RANGE_GUARD=0
-# leaves the flag to the caller (ops.check_range)
+# The one switch of this file: the range guard of the split-precision convs, enforced per eager forward
+# (see forward); FSMI_RANGE_GUARD=0, or a caller that checks ops.check_range() itself and sets the
+# attribute, leaves the flag to the caller.  update.OVERLAP (bench.py) also decides whether the context
+# net (+ stem_2, CAM / SAM), the FeatureAtt gates and the hourglass's disparity-transformer branch run on
+# side streams beside the 3D path.
 RANGE_GUARD = os.environ.get("FSMI_RANGE_GUARD", "1") != "0"
-
 
 
 def _gated(seq, x, gate):
@@ -129,7 +128,7 @@ class hourglass(nn.Module):
     def forward(self, x, features, gates=None):
         """``gates``: precomputed ``gate_logits(features)`` (ready on the current stream)."""
         dt_s = None
-        if _update.OVERLAP and CTX_OVERLAP and self._dt_fast(x, x):
+        if _update.OVERLAP and self._dt_fast(x, x):
             # the disparity transformer branch (patch embed + 4 encoder layers, ~0.45 ms at cfg2, a few
             # hundred waves) reads only x: it runs on a side stream beside conv1 .. conv1_up
             main = torch.cuda.current_stream(x.device)
@@ -171,8 +170,7 @@ class hourglass(nn.Module):
 
     def _dt_fast(self, x, conv) -> bool:
         pc, bn = self.conv_patch[0], self.conv_patch[1]
-        return (x.is_cuda and x.dtype in _sub.HIP_DTYPES and conv.dtype in _sub.HIP_DTYPES and not self.training
-                and not torch.is_grad_enabled() and _sub.DT_FAST
+        return (_sub._hip(x) and conv.dtype in _sub.HIP_DTYPES and not self.training and _sub.DT_FAST
                 and pc.groups == pc.in_channels == pc.out_channels and pc.kernel_size == (4, 4, 4)
                 and pc.stride == (4, 4, 4) and pc.padding == (0, 0, 0) and bn.track_running_stats
                 and all(n % 4 == 0 for n in x.shape[2:]) and tuple(conv.shape) == tuple(x.shape))
@@ -180,17 +178,15 @@ class hourglass(nn.Module):
     def _patch_fold(self):
         """conv_patch bias + eval BatchNorm3d as per-channel (scale, shift), cached per version."""
         pc, bn = self.conv_patch[0], self.conv_patch[1]
-        ts = [pc.weight, pc.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        key = tuple((t.data_ptr(), t._version) for t in ts if t is not None)
-        hit = self.__dict__.get("_fsmi_patch")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                inv = (bn.running_var.double() + bn.eps).rsqrt() * (bn.weight.double() if bn.weight is not None else 1)
-                b = pc.bias.double() if pc.bias is not None else torch.zeros_like(inv)
-                shift = (b - bn.running_mean.double()) * inv + (bn.bias.double() if bn.bias is not None else 0)
-                hit = (key, inv.float().contiguous(), shift.float().contiguous())
-            self.__dict__["_fsmi_patch"] = hit
-        return hit[1], hit[2]
+
+        def build():
+            inv = (bn.running_var.double() + bn.eps).rsqrt() * (bn.weight.double() if bn.weight is not None else 1)
+            b = pc.bias.double() if pc.bias is not None else torch.zeros_like(inv)
+            shift = (b - bn.running_mean.double()) * inv + (bn.bias.double() if bn.bias is not None else 0)
+            return inv.float().contiguous(), shift.float().contiguous()
+
+        return _sub._cached(self, "_fsmi_patch", [pc.weight, pc.bias, bn.weight, bn.bias, bn.running_mean,
+                                                  bn.running_var], build)
 
 
 def _poison_outputs(out):
@@ -251,26 +247,24 @@ class FoundationStereo(nn.Module):
         r = self.args.corr_radius
         self.dx = torch.linspace(-r, r, 2 * r + 1, requires_grad=False).reshape(1, 1, 2 * r + 1, 1)
         self.fused_volume = True
-        self._stem_cache = None
 
     # ------------------------------------------------------------ volume build
     def _stem_weights(self):
         """Fold proj_cmb into the concat columns of corr_stem[0] (exact algebra, fp64)."""
         stem, proj = self.corr_stem[0], self.proj_cmb
-        key = tuple((t.data_ptr(), t._version) for t in (stem.weight, stem.bias, proj.weight, proj.bias))
-        if self._stem_cache is None or self._stem_cache[0] != key:
-            with torch.no_grad():
-                S = stem.weight.reshape(stem.weight.shape[0], -1).double()       # (Cs, 32)
-                sb = stem.bias.double()
-                P = proj.weight.reshape(proj.weight.shape[0], -1).double()        # (12, C)
-                pb = proj.bias.double()
-                G = self.cv_group
-                Sl, Sr = S[:, G:G + 12], S[:, G + 12:G + 24]
-                wa, ba = Sl @ P, Sl @ pb + sb
-                wb, bb = Sr @ P, Sr @ pb
-                tensors = [t.float().contiguous() for t in (S[:, :G], wa, ba, wb, bb)]
-            self._stem_cache = (key, tensors)
-        return self._stem_cache[1]
+
+        def build():
+            S = stem.weight.reshape(stem.weight.shape[0], -1).double()       # (Cs, 32)
+            sb = stem.bias.double()
+            P = proj.weight.reshape(proj.weight.shape[0], -1).double()        # (12, C)
+            pb = proj.bias.double()
+            G = self.cv_group
+            Sl, Sr = S[:, G:G + 12], S[:, G + 12:G + 24]
+            wa, ba = Sl @ P, Sl @ pb + sb
+            wb, bb = Sr @ P, Sr @ pb
+            return [t.float().contiguous() for t in (S[:, :G], wa, ba, wb, bb)]
+
+        return _sub._cached(self, "_fsmi_stem", [stem.weight, stem.bias, proj.weight, proj.bias], build)
 
     def build_stem_volume(self, fl0, fr0):
         """gwc + concat + corr_stem[0] -> (B, 28, D4, H4, W4) (core/foundation_stereo.py:207-213)."""
@@ -342,22 +336,18 @@ class FoundationStereo(nn.Module):
         with autocast(mp, md):
             features_left, features_right, vit_feat = self._backbone(image1, image2)
             ctx_s = None
-            ctx_overlap = _update.OVERLAP and CTX_OVERLAP and image1.is_cuda and not torch.is_grad_enabled()
+            ctx_overlap = _update.OVERLAP and image1.is_cuda and not torch.is_grad_enabled()
             corr_pyr = None
-            # the cost-volume build and the all-pairs correlation pyramid run ALONE on the chip, before any
-            # side stream forks (the volume pyramid follows the hourglass on the main stream, before the
-            # classifier): the north star's two HBM / MFMA kernels measured without co-running convs
-            geo_alone = ctx_overlap
-            if geo_alone:
+            if ctx_overlap:
                 # the two HBM / MFMA kernels the north star measures run ALONE on the chip, before any
                 # side stream forks: the cost-volume build, then the all-pairs correlation pyramid (it
                 # needs only the features; the side streams' convs used to stretch it 10x beside the
-                # classifier).  ~70 us on the main stream; the side streams are far off the critical path
+                # classifier).  ~70 us on the main stream; the side streams are far off the critical path.
+                # (The volume pyramid follows the hourglass on the main stream, before the classifier.)
                 vol = self.build_stem_volume(features_left[0], features_right[0])
                 corr_pyr = Combined_Geo_Encoding_Volume.corr_pyramid(features_left[0].float(),
                                                                      features_right[0].float(),
                                                                      self.args.corr_levels)
-            if ctx_overlap:
                 # stem_2 + context net + CAM / SAM read only the images and vit_feat: a side stream
                 # runs them beside the volume build and the 3D filtering (joined before the loop)
                 main = torch.cuda.current_stream(image1.device)
@@ -381,7 +371,7 @@ class FoundationStereo(nn.Module):
                         self.cost_agg.gate_logits(features_left)
                     g_ev = torch.cuda.Event()
                     g_ev.record(g_s)
-            if not geo_alone:
+            if not ctx_overlap:
                 vol = self.build_stem_volume(features_left[0], features_right[0])
             if fuse:
                 # corr_feature_att's sigmoid(gate) * vol in the last ResNet block's epilogue; the gates
@@ -425,7 +415,7 @@ class FoundationStereo(nn.Module):
         overlap = _update.OVERLAP and _update._fast(disp)
         if overlap:     # fp32 state for the HIP loop (fp16 / bf16 context features under autocast)
             net_list, inp_list, att = _update._f32s(net_list), _update._f32s(inp_list), _update._f32s(att)
-        if overlap and test_mode and self.args.n_gru_layers == 3 and iters > 0 and _update.PIPELINE:
+        if overlap and test_mode and self.args.n_gru_layers == 3 and iters > 0:
             # gru16 / gru08 one iteration ahead on their own stream (same math, see run_pipelined)
             net_list, mask_feat_4, disp = self.update_block.run_pipelined(net_list, inp_list, geo_fn,
                                                                           disp.detach(), att, iters, pre=ctx_pre)

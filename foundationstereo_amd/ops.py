@@ -100,15 +100,14 @@ def comb_volume_stem(fl: Tensor, fr: Tensor, A: Tensor, Bm: Tensor, Wg: Tensor, 
                      two_pass: bool = False) -> Tensor:
     """Fused gwc + concat + corr_stem[0] (core/foundation_stereo.py:207-213,165) -> (B,Cs,D,H,W).
 
-    Default: one LDS-staged streaming kernel (no scratch); ``two_pass`` (or
-    FSMI_BUILD_TWO_PASS=1): gwc into a (B,G,D,H,W) scratch, then a stem pass."""
+    Default: one LDS-staged streaming kernel (no scratch); ``two_pass``: gwc into a
+    (B,G,D,H,W) scratch, then a stem pass."""
     _check("comb_volume_stem", fl, fr, A, Bm, Wg)
     B, C, H, W = fl.shape
     Cs, G = Wg.shape
     assert C % G == 0, f"C:{C}, num_groups:{G}"
     fl, fr, A, Bm, Wg = _c(fl), _c(fr), _c(A), _c(Bm), _c(Wg)
     out = torch.empty((B, Cs, maxdisp, H, W), device=fl.device, dtype=torch.float32)
-    two_pass = two_pass or os.environ.get("FSMI_BUILD_TWO_PASS", "0") == "1"
     ws = torch.empty((B, G, maxdisp, H, W), device=fl.device, dtype=torch.float32) if two_pass else None
     _lib.check(_lib.load().fsmi_comb_volume_stem(_p(fl), _p(fr), _p(A), _p(Bm), _p(Wg),
                                                  _p(ws) if ws is not None else None, _p(out), B, C, G, Cs,
@@ -413,8 +412,6 @@ def conv3d(x: Tensor, pk, bias: Tensor = None, act=None, res: Tensor = None, res
     stream = _stream(x)
     ws = _split_workspace(x.device, stream, 8 * B * pk.cout * Do * Ho * Wo)
     cfg, nsplit = _tuned(pk.k if stride == 1 else f"{pk.k}s2", pk.kd, Cin, pk.cout, B, D, H, W, cfg, nsplit)
-    if cfg == 30 and not _DEPTH_TILE:
-        cfg, nsplit = -1, -1           # A/B: the generic volume tiles (the C side picks)
     _lib.check(_lib.load().fsmi_conv3d_halo_x3_ex(
         _p(x), Cin, _p(pk.whi), _p(pk.wlo), _p(pk.scale_bias(bias)),
         _p(res) if res is not None else None, _p(fatt) if fatt is not None else None, _p(out), B, pk.cout,
@@ -600,7 +597,11 @@ def _tuned(ks, kd, cin, cout, B, D, H, W, cfg, nsplit):
     return cfg, nsplit
 
 
-# A/B knob: no split-K for 2D maps of at most this many pixels (the 1/8 and 1/16 GRU levels run on
+# The switches of this file and who uses them: FSMI_TUNE_PATH / FSMI_TUNE_DB (tools/tune_conv.py, and
+# bench runs on a candidate table), _SPLIT_MAXPIX (tests/test_gpu_range.py sets it),
+# _SPLIT_CAP (tools/insitu_tune.py), _RANGE_DEBUG (FSMI_RANGE_DEBUG: a sync + range check after each conv).
+#
+# _SPLIT_MAXPIX: no split-K for 2D maps of at most this many pixels (the 1/8 and 1/16 GRU levels run on
 # a side stream beside gru04, so the chip is already busy and split-K only adds the reduce pass)
 _SPLIT_MAXPIX = int(os.environ.get("FSMI_SPLIT_MAXPIX", "0"))
 # Cap on the split-K factor of auto-chosen layers (0: none).  The table is timed one layer at a
@@ -608,9 +609,6 @@ _SPLIT_MAXPIX = int(os.environ.get("FSMI_SPLIT_MAXPIX", "0"))
 # a deep split was chosen to fill, and the extra partial-sum traffic remains.  Measured end to end
 # (cfg2, two runs each): cap 2 +1.3 %, cap 3 -1.2 %, cap 1 -12 %; cfg3 (4 pairs / GPU) neutral.
 _SPLIT_CAP = int(os.environ.get("FSMI_SPLIT_CAP", "2"))
-# (17, 1, 1) volume convs (Conv3dNormActReduced.conv2) on the depth-blocked tile (cfg 30); 0: the
-# generic volume tiles from the tuning table (A/B)
-_DEPTH_TILE = os.environ.get("FSMI_DEPTH_TILE", "1") != "0"
 
 
 _SPLIT_WS = {}

@@ -19,8 +19,6 @@ torch path uses PyTorch SDPA in place of the reference's third-party
 """
 from __future__ import annotations
 
-import os
-
 import math
 
 import torch
@@ -52,21 +50,15 @@ class LayerNorm2d(nn.LayerNorm):
         return y.permute(0, 3, 1, 2).contiguous()
 
 
-FILTER3D = os.environ.get("FSMI_FILTER3D", "1") != "0"
-# The hourglass ConvTranspose3d *_up on the halo kernel's 2x2x2 phase tiles (all 8 output phases in
-# one launch; tools/up3d_bench.py at cfg2: conv1_up 296 us, conv2_up 139 us, conv3_up 64 us vs
-# 711 / 249 / 97 us for MIOpen / CK + BatchNorm + LeakyReLU).  UP3D_MINVOX: smallest input volume
-# sent there (A/B knob).
-UP3D = os.environ.get("FSMI_UP3D", "1") != "0"
-UP3D_MINVOX = int(os.environ.get("FSMI_UP3D_MINVOX", "0"))
-DT_FAST = os.environ.get("FSMI_DT", "1") != "0"
-# the spx ConvTranspose2d(k=4, s=2, p=1) pair (spx_2_gru.conv1, spx_gru) on the halo kernel's 2x2 phase
-# tiles (FSMI_UP2D=0: MIOpen, for A/B)
-UP2D = os.environ.get("FSMI_UP2D", "1") != "0"
-# stride-2 3x3x3 convs on the halo kernel's stride-2 tiles (FSMI_S2=0: MIOpen, for A/B)
-S2_3D = os.environ.get("FSMI_S2", "1") != "0"
-# FeatureAtt's sigmoid(gate) * cv folded into the producing conv's epilogue (FSMI_FATT=0: ATen)
-FATT_FUSE = os.environ.get("FSMI_FATT", "1") != "0"      # disparity transformer on csrc/transformer.hip
+# Module attributes that switch a HIP path off (set by tests, never read from the environment):
+#   S2_3D      stride-2 convs on the halo kernel's stride-2 tiles; False: MIOpen (tests/test_gpu_fast.py's
+#              and test_gpu_parity.py's reference for those tiles)
+#   FATT_FUSE  FeatureAtt's sigmoid(gate) * cv in the producing conv's epilogue; False: ATen
+#              (tests/test_gpu_fast.py)
+#   DT_FAST    the disparity transformer on csrc/transformer.hip; False: the torch layers (tests/test_gpu_dt.py)
+S2_3D = True
+FATT_FUSE = True
+DT_FAST = True
 
 
 # Input dtypes the HIP paths accept.  Under the reference's fp16 autocast (scripts/run_demo.py:161)
@@ -79,75 +71,96 @@ def _f32(x):
     return x if x.dtype == torch.float32 else x.float()
 
 
-def _fast3d(x, conv, bn) -> bool:
-    """Stride-1 'same' Conv3d (+ eval BatchNorm3d) that the halo kernel runs (no grad; fp32
+def _cached(mod, slot, tensors, build):
+    """``build()`` (run under no_grad) cached in ``mod.__dict__[slot]`` until any of ``tensors`` (None
+    entries skipped) is replaced or modified in place.  While none changes every call returns the same
+    objects: captured graphs read the buffers a pack pins (``PackedConv.scale_bias``).  The key is
+    (address, version) per tensor: a storage swapped through ``.data`` (``module.to(dtype)``), which keeps
+    the version, onto an address the allocator recycled from the old storage is not seen."""
+    key = tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
+    hit = mod.__dict__.get(slot)
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            hit = (key, build())
+        mod.__dict__[slot] = hit
+    return hit[1]
+
+
+def _hip(x) -> bool:
+    """The tensor half of every HIP-path test: a ROCm tensor of an accepted dtype, no grad (fp32
     compute, also under autocast)."""
-    if not (FILTER3D and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-            and type(conv) is nn.Conv3d):
-        return False
-    kd, kh, kw = conv.kernel_size
-    if conv.stride != (1, 1, 1) or conv.dilation != (1, 1, 1) or conv.groups != 1 or kh != kw or kh not in (1, 3) \
-            or kd % 2 == 0 or conv.padding != (kd // 2, kh // 2, kw // 2):
-        return False
-    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is nn.BatchNorm3d and not bn.training
+    return x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
+
+
+def _bn_folds(bn, cls) -> bool:
+    """No norm, or one that folds into the packed weights: an eval ``cls`` with running statistics."""
+    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is cls and not bn.training
                                                          and bn.track_running_stats)
 
 
-def _fast_s2_3d(x, conv, bn) -> bool:
-    """Conv3d(k=3, s=2, p=1) (+ eval BatchNorm3d): the hourglass downsampling convs
-    (core/foundation_stereo.py:50-58) on the halo kernel's stride-2 tiles."""
-    if not (FILTER3D and S2_3D and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-            and type(conv) is nn.Conv3d):
-        return False
-    if conv.kernel_size != (3, 3, 3) or conv.stride != (2, 2, 2) or conv.padding != (1, 1, 1) \
-            or conv.dilation != (1, 1, 1) or conv.groups != 1:
-        return False
-    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is nn.BatchNorm3d and not bn.training
-                                                         and bn.track_running_stats)
+def _conv_kind(conv):
+    """The halo-kernel tile family a conv module runs on, from its attributes alone:
+    's1'  stride-1 'same' Conv2d / Conv3d, 1x1 or 3x3 taps in the plane, any odd depth;
+    's2'  Conv3d(k=3, s=2, p=1), Conv2d(k=3, s=2, p=1) or Conv2d(k=1, s=2, p=0);
+    'up'  ConvTranspose2d / ConvTranspose3d(k=4, s=2, p=1), no output padding;
+    None  anything else (dilated, grouped, other kernels or paddings, not a conv)."""
+    if type(conv) not in (nn.Conv2d, nn.Conv3d, nn.ConvTranspose2d, nn.ConvTranspose3d):
+        return None
+    k, s, p = conv.kernel_size, conv.stride, conv.padding
+    n = len(k)
+    if conv.dilation != (1,) * n or conv.groups != 1:
+        return None
+    if type(conv) in (nn.ConvTranspose2d, nn.ConvTranspose3d):
+        return "up" if (k, s, p, conv.output_padding) == ((4,) * n, (2,) * n, (1,) * n, (0,) * n) else None
+    if p != tuple(i // 2 for i in k):
+        return None
+    if s == (1,) * n:
+        return "s1" if k[-2] == k[-1] and k[-1] in (1, 3) and k[0] % 2 == 1 else None
+    if s == (2,) * n:
+        return "s2" if k == (3,) * n or k == (1, 1) else None
+    return None
 
 
-def _fast_s2_2d(x, conv, bn) -> bool:
-    """Conv2d(k=3, s=2, p=1) or Conv2d(k=1, s=2, p=0) (+ eval BatchNorm2d): the context net's
-    downsampling convs, as depth-1 volumes on the halo kernel's stride-2 tiles."""
-    if not (FILTER3D and S2_3D and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-            and type(conv) is nn.Conv2d):
-        return False
-    k = conv.kernel_size
-    if k not in ((3, 3), (1, 1)) or conv.stride != (2, 2) or conv.padding != (k[0] // 2, k[1] // 2) \
-            or conv.dilation != (1, 1) or conv.groups != 1:
-        return False
-    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is nn.BatchNorm2d and not bn.training
-                                                         and bn.track_running_stats)
+def _route(x, conv, bn=None, nd=2):
+    """``_conv_kind`` of an ``nd``-D conv (+ ``bn``) when act(bn(conv(x))) runs on the HIP conv engine
+    (``conv2d_bn_act`` / ``conv2d_s2_bn_act`` / ``deconv2d_bn_act``; 3D: ``conv3d_bn_act``,
+    ``ops.conv3d_up2``), else None: the layer stays on torch."""
+    kind = _conv_kind(conv)
+    if kind is None or len(conv.kernel_size) != nd or not _hip(x) or (kind == "s2" and not S2_3D):
+        return None
+    return kind if _bn_folds(bn, nn.BatchNorm3d if nd == 3 else nn.BatchNorm2d) else None
 
 
 def conv2d_s2_bn_act(x, conv, bn, act=None, res=None, res_pre=False):
-    """act(bn(conv(x)) [+ res]) for a stride-2 Conv2d (``_fast_s2_2d``): the volume kernel on
+    """act(bn(conv(x)) [+ res]) for a stride-2 Conv2d (``_route`` 's2'): the volume kernel on
     (B, C, 1, H, W)."""
     pk, b = _packed_bn(conv, bn)
     r = None if res is None else _f32(res).unsqueeze(2)
     return ops.conv3d(_f32(x).unsqueeze(2), pk, bias=b, act=act, res=r, res_pre=res_pre, stride=2).squeeze(2)
 
 
-def conv_any(conv, x):
-    """conv(x) for a bare (no-norm) Conv2d: stride 1 on the halo kernel, 3x3 s2 / 1x1 s2 on its stride-2
-    tiles, anything else (incl. fp16 output under autocast when the input is fp16) through torch."""
-    if type(conv) is nn.Conv2d:
-        if _fast2d(x, conv, None):
-            return conv2d_bn_act([x], conv, None)
-        if _fast_s2_2d(x, conv, None):
-            return conv2d_s2_bn_act(x, conv, None)
+def _conv2d_hip(conv, x):
+    """conv(x) for a bare (no-norm) Conv2d / ConvTranspose2d: on the HIP conv engine where ``_route`` finds
+    a tile for it, anything else (incl. fp16 output under autocast when the input is fp16) through torch."""
+    kind = _route(x, conv)
+    if kind == "s1":
+        return conv2d_bn_act([x], conv, None)
+    if kind == "s2":
+        return conv2d_s2_bn_act(x, conv, None)
+    if kind == "up":
+        return deconv2d_bn_act(x, conv)
     return conv(x)
 
 
 def run_seq(seq, x):
-    """nn.Sequential forward with its bare Conv2d layers through ``conv_any`` and its InstanceNorm2d
+    """nn.Sequential forward with its bare Conv2d layers through ``_conv2d_hip`` and its InstanceNorm2d
     (+ a following ReLU / LeakyReLU) through ``ops.instance_norm``."""
     mods = list(seq)
     i = 0
     while i < len(mods):
         m = mods[i]
         if type(m) is nn.Conv2d:
-            x = conv_any(m, x)
+            x = _conv2d_hip(m, x)
         elif _hip_in(m, x):
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             act = "relu" if type(nxt) is nn.ReLU else ("leaky" if type(nxt) is nn.LeakyReLU
@@ -160,30 +173,9 @@ def run_seq(seq, x):
     return x
 
 
-def _fast_up3d(x, conv, bn) -> bool:
-    """ConvTranspose3d(k=4, s=2, p=1) (+ eval BatchNorm3d) that the 2x2x2 phase tiles run."""
-    if not (FILTER3D and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-            and type(conv) is nn.ConvTranspose3d):
-        return False
-    if conv.kernel_size != (4, 4, 4) or conv.stride != (2, 2, 2) or conv.padding != (1, 1, 1) \
-            or conv.output_padding != (0, 0, 0) or conv.dilation != (1, 1, 1) or conv.groups != 1:
-        return False
-    if x.shape[2] * x.shape[3] * x.shape[4] < UP3D_MINVOX:
-        return False
-    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is nn.BatchNorm3d and not bn.training
-                                                         and bn.track_running_stats)
-
-
 def fast_up2d(x, conv, bn=None) -> bool:
     """ConvTranspose2d(k=4, s=2, p=1) (+ eval BatchNorm2d) that the 2x2 phase tiles run."""
-    if not (UP2D and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-            and type(conv) is nn.ConvTranspose2d):
-        return False
-    if conv.kernel_size != (4, 4) or conv.stride != (2, 2) or conv.padding != (1, 1) \
-            or conv.output_padding != (0, 0) or conv.dilation != (1, 1) or conv.groups != 1:
-        return False
-    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is nn.BatchNorm2d and not bn.training
-                                                         and bn.track_running_stats)
+    return _route(x, conv, bn) == "up"
 
 
 def deconv2d_bn_act(x, conv, bn=None, act=None):
@@ -192,94 +184,58 @@ def deconv2d_bn_act(x, conv, bn=None, act=None):
     return ops.conv2d_up2(_f32(x), packs, bias=b, act=act)
 
 
-def _packed_up(conv, bn):
-    """The 8 (4) phase packs of a ConvTranspose3d (2d) with its eval BatchNorm folded (fp64 fold), cached."""
-    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else [])
-    is_bn = isinstance(bn, (nn.BatchNorm2d, nn.BatchNorm3d))
-    if is_bn:
-        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    key = tuple((t.data_ptr(), t._version) for t in ts)
-    hit = conv.__dict__.get("_fsmi_pack_up")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            cout = conv.weight.shape[1]
-            b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(
-                cout, dtype=torch.float64, device=conv.weight.device)
-            sc = None
-            if is_bn:
-                sc = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-                b = (b - bn.running_mean.double()) * sc + bn.bias.double()
-            pack = ops.pack_deconv2d_phases if conv.weight.dim() == 4 else ops.pack_deconv_phases
-            hit = (key, pack(conv.weight, sc), b.float().contiguous())
-        conv.__dict__["_fsmi_pack_up"] = hit
-    return hit[1], hit[2]
-
-
-def _fast2d(x, conv, bn) -> bool:
-    """Stride-1 'same' Conv2d (1x1 / 3x3, + eval BatchNorm2d) that the halo kernel runs."""
-    if not (FILTER3D and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-            and type(conv) is nn.Conv2d):
-        return False
-    kh, kw = conv.kernel_size
-    if conv.stride != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1 or kh != kw or kh not in (1, 3) \
-            or conv.padding != (kh // 2, kw // 2):
-        return False
-    return bn is None or isinstance(bn, nn.Identity) or (type(bn) is nn.BatchNorm2d and not bn.training
-                                                         and bn.track_running_stats)
-
-
 def _hip_in(norm, x) -> bool:
     """An eval-style InstanceNorm2d (no affine, no running statistics: nn.InstanceNorm2d's defaults, as
     every InstanceNorm of the reference) that ``ops.instance_norm`` runs."""
-    return (type(norm) is nn.InstanceNorm2d and not norm.affine and not norm.track_running_stats and x.is_cuda
-            and x.dtype in HIP_DTYPES and x.dim() == 4 and not torch.is_grad_enabled() and FILTER3D)
+    return (type(norm) is nn.InstanceNorm2d and not norm.affine and not norm.track_running_stats and _hip(x)
+            and x.dim() == 4)
 
 
-def _conv2d_hip(conv, x):
-    """A bare Conv2d / ConvTranspose2d(k4 s2 p1) on the HIP conv engine, or None when it does not apply."""
-    if type(conv) is nn.Conv2d:
-        if _fast2d(x, conv, None):
-            return conv2d_bn_act([x], conv, None)
-        if _fast_s2_2d(x, conv, None):
-            return conv2d_s2_bn_act(x, conv, None)
-    elif fast_up2d(x, conv, None):
-        return deconv2d_bn_act(x, conv)
-    return None
+def _folded(conv, bn, slot, pack):
+    """``(pack(sc), bias)`` of a conv with its eval BatchNorm folded in, in fp64: per output channel
+    sc = gamma / sqrt(var + eps) (None without a BatchNorm) and bias = (b - mean) * sc + beta.  Cached
+    on the conv module, rebuilt when any parameter or running statistic changes."""
+    is_bn = isinstance(bn, (nn.BatchNorm2d, nn.BatchNorm3d))
+
+    def build():
+        b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(
+            conv.out_channels, dtype=torch.float64, device=conv.weight.device)
+        sc = None
+        if is_bn:
+            sc = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+            b = (b - bn.running_mean.double()) * sc + bn.bias.double()
+        return pack(sc), b.float().contiguous()
+
+    return _cached(conv, slot, [conv.weight, conv.bias] + (
+        [bn.weight, bn.bias, bn.running_mean, bn.running_var] if is_bn else []), build)
+
+
+def _packed_up(conv, bn):
+    """The 8 (4) phase packs of a ConvTranspose3d (2d) with its eval BatchNorm folded, and the bias."""
+    pack = ops.pack_deconv2d_phases if conv.weight.dim() == 4 else ops.pack_deconv_phases
+    return _folded(conv, bn, "_fsmi_pack_up", lambda sc: pack(conv.weight, sc))
 
 
 def _packed_bn(conv, bn):
-    """Halo-kernel weights of a Conv2d/Conv3d with its eval BatchNorm folded in (fp64 fold),
-    cached on the conv module, rebuilt when any parameter or running statistic changes."""
-    ts = [conv.weight] + ([conv.bias] if conv.bias is not None else [])
-    is_bn = isinstance(bn, (nn.BatchNorm2d, nn.BatchNorm3d))
-    if is_bn:
-        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    key = tuple((t.data_ptr(), t._version) for t in ts)
-    hit = conv.__dict__.get("_fsmi_pack_bn")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            w = conv.weight.detach().double()
-            b = conv.bias.detach().double() if conv.bias is not None else torch.zeros(w.shape[0], dtype=w.dtype,
-                                                                                       device=w.device)
-            if is_bn:
-                sc = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-                w = w * sc.view((-1,) + (1,) * (w.dim() - 1))
-                b = (b - bn.running_mean.double()) * sc + bn.bias.double()
-            hit = (key, ops.PackedConv(w.float(), mode="halo"), b.float().contiguous())
-        conv.__dict__["_fsmi_pack_bn"] = hit
-    return hit[1], hit[2]
+    """Halo-kernel weights of a Conv2d / Conv3d with its eval BatchNorm folded in, and the bias."""
+    def pack(sc):
+        w = conv.weight.detach().double()
+        if sc is not None:
+            w = w * sc.view((-1,) + (1,) * (w.dim() - 1))
+        return ops.PackedConv(w.float(), mode="halo")
+    return _folded(conv, bn, "_fsmi_pack_bn", pack)
 
 
 def conv2d_bn_act(segs, conv, bn, act=None, **kw):
-    """act(bn(conv(cat(segs)))) on the 2D halo kernel (see ``_fast2d``); ``segs`` as ops.conv2d."""
+    """act(bn(conv(cat(segs)))) on the 2D halo kernel (``_route`` 's1'); ``segs`` as ops.conv2d."""
     pk, b = _packed_bn(conv, bn)
     segs = [_f32(s) if isinstance(s, torch.Tensor) else (_f32(s[0]),) + tuple(s[1:]) for s in segs]
     return ops.conv2d(segs, pk, bias=b, act=act, **kw)
 
 
 def conv3d_bn_act(x, conv, bn, act=None, res=None, res_pre=False, fatt=None):
-    """act(bn(conv(x)) [+ res]) [* sigmoid(fatt)] on the halo kernel (``_fast3d`` / ``_fast_s2_3d``
-    say when it applies; the conv's stride is taken from the module)."""
+    """act(bn(conv(x)) [+ res]) [* sigmoid(fatt)] on the halo kernel (``_route`` 's1' / 's2' of a
+    Conv3d; the conv's stride is taken from the module)."""
     pk, b = _packed_bn(conv, bn)
     return ops.conv3d(_f32(x), pk, bias=b, act=act, res=None if res is None else _f32(res), res_pre=res_pre,
                       stride=conv.stride[0], fatt=None if fatt is None else _f32(fatt))
@@ -308,19 +264,22 @@ class BasicConv(nn.Module):
 
     def forward(self, x):
         bn = self.bn if self.use_bn else None
-        if _fast3d(x, self.conv, bn) or _fast_s2_3d(x, self.conv, bn):   # 3D conv + folded BN + LeakyReLU
-            return conv3d_bn_act(x, self.conv, bn, "leaky" if self.relu else None)
-        if UP3D and _fast_up3d(x, self.conv, bn):   # ConvTranspose3d k4 s2: 8 phase convs, BN folded
+        act = "leaky" if self.relu else None
+        nd = self.conv.weight.dim() - 2
+        kind = _route(x, self.conv, bn, nd)
+        if nd == 3 and kind == "up":                # ConvTranspose3d k4 s2: 8 phase convs, BN folded
             packs, b = _packed_up(self.conv, bn)
-            return ops.conv3d_up2(_f32(x), packs, bias=b, act="leaky" if self.relu else None)
-        if _fast2d(x, self.conv, bn):
-            return conv2d_bn_act([x], self.conv, bn, "leaky" if self.relu else None)
-        if fast_up2d(x, self.conv, bn):             # ConvTranspose2d k4 s2: 4 phase convs, BN folded
-            return deconv2d_bn_act(x, self.conv, bn, "leaky" if self.relu else None)
-        if bn is not None and _hip_in(bn, x):       # norm='instance': conv, then InstanceNorm + LeakyReLU
-            y = _conv2d_hip(self.conv, x)
-            if y is not None:
-                return ops.instance_norm(y, act="leaky" if self.relu else None, eps=bn.eps)
+            return ops.conv3d_up2(_f32(x), packs, bias=b, act=act)
+        if nd == 3 and kind:                        # 3D conv (stride 1 / 2) + folded BN + LeakyReLU
+            return conv3d_bn_act(x, self.conv, bn, act)
+        if kind == "s1":
+            return conv2d_bn_act([x], self.conv, bn, act)
+        if kind == "up":                            # ConvTranspose2d k4 s2: 4 phase convs, BN folded
+            return deconv2d_bn_act(x, self.conv, bn, act)
+        # (a stride-2 Conv2d + BatchNorm stays on MIOpen here; ResidualBlock runs the context net's)
+        if bn is not None and _hip_in(bn, x) and _route(x, self.conv):
+            # norm='instance': conv, then InstanceNorm + LeakyReLU
+            return ops.instance_norm(_conv2d_hip(self.conv, x), act=act, eps=bn.eps)
         x = self.bn(self.conv(x)) if self.use_bn else self.conv(x)
         return F.leaky_relu(x, 0.01) if self.relu else x
 
@@ -344,8 +303,8 @@ class Conv3dNormActReduced(nn.Module):
         """``fatt``: a following FeatureAtt's pre-sigmoid gate (``FeatureAtt.logits``), applied in the
         second conv's epilogue (returns sigmoid(fatt).unsqueeze(2) * block(x))."""
         c1, c2 = self.conv1, self.conv2
-        if _fast3d(x, c1[0], c1[1]) and _fast3d(x, c2[0], c2[1]) and isinstance(c1[2], nn.ReLU) \
-                and isinstance(c2[2], nn.ReLU):
+        if _route(x, c1[0], c1[1], 3) == "s1" and _route(x, c2[0], c2[1], 3) == "s1" \
+                and isinstance(c1[2], nn.ReLU) and isinstance(c2[2], nn.ReLU):
             y = conv3d_bn_act(x, c1[0], c1[1], "relu")
             return conv3d_bn_act(y, c2[0], c2[1], "relu", fatt=fatt)
         y = self.conv2(self.conv1(x))
@@ -380,12 +339,13 @@ class _ResBlock(nn.Module):
         (returns sigmoid(fatt).unsqueeze(2) * block(x))."""
         bn1 = self.bn1 if self.norm_layer is not None else None
         bn2 = self.bn2 if self.norm_layer is not None else None
-        if self.downsample is None and _fast3d(x, self.conv1, bn1) and _fast3d(x, self.conv2, bn2):
+        if self.downsample is None and _route(x, self.conv1, bn1, 3) == "s1" \
+                and _route(x, self.conv2, bn2, 3) == "s1":
             y = conv3d_bn_act(x, self.conv1, bn1, "relu")
             # relu(bn2(conv2) + x) [* sigmoid(fatt)]
             return conv3d_bn_act(y, self.conv2, bn2, "relu", res=x, res_pre=True, fatt=fatt)
         if (self.downsample is None and fatt is None and bn1 is not None and _hip_in(bn1, x) and _hip_in(bn2, x)
-                and _fast2d(x, self.conv1, None) and _fast2d(x, self.conv2, None)):
+                and _route(x, self.conv1) == "s1" and _route(x, self.conv2) == "s1"):
             # InstanceNorm variant (Conv2x_IN's conv2): relu(IN(conv2(relu(IN(conv1 x)))) + x)
             x = _f32(x)
             y = ops.instance_norm(conv2d_bn_act([x], self.conv1, None), act="relu", eps=bn1.eps)
@@ -514,7 +474,7 @@ class Conv2x(nn.Module):
             x = F.interpolate(x, size=(rem.shape[-2], rem.shape[-1]), mode="bilinear")
         c2 = self.conv2
         bn2 = c2.bn if c2.use_bn else None
-        if self.concat and not self.is_3d and x.shape[1] % 8 == 0 and _fast2d(x, c2.conv, bn2):
+        if self.concat and not self.is_3d and x.shape[1] % 8 == 0 and _route(x, c2.conv, bn2) == "s1":
             # the cat read in place: conv2's input is the two segments (x, rem)
             return conv2d_bn_act([x, rem], c2.conv, bn2, "leaky" if c2.relu else None)
         x = torch.cat((x, rem), 1) if self.concat else x + rem
@@ -534,11 +494,9 @@ class BasicConv_IN(nn.Module):
         self.IN = nn.InstanceNorm3d(out_channels) if is_3d else nn.InstanceNorm2d(out_channels)
 
     def forward(self, x):
-        if self.use_in and _hip_in(self.IN, x):
-            y = _conv2d_hip(self.conv, x)
-            if y is not None:
-                return ops.instance_norm(y, act="leaky" if self.relu else None, eps=self.IN.eps)
-        x = conv_any(self.conv, x)
+        if self.use_in and _hip_in(self.IN, x) and _route(x, self.conv):
+            return ops.instance_norm(_conv2d_hip(self.conv, x), act="leaky" if self.relu else None, eps=self.IN.eps)
+        x = _conv2d_hip(self.conv, x)
         if self.use_in:
             x = self.IN(x)
         return F.leaky_relu(x, 0.01) if self.relu else x
@@ -631,9 +589,7 @@ class FeatureAtt(nn.Module):
         when they qualify (the hourglass folds sigmoid(gate) * cv into the producing conv)."""
         c0, c1 = self.feat_att
         h = c0(feat)
-        if _fast2d(h, c1, None):
-            return conv2d_bn_act([h], c1, None)
-        return c1(h)
+        return conv2d_bn_act([h], c1, None) if _route(h, c1) == "s1" else c1(h)
 
     def forward(self, cv, feat):
         return torch.sigmoid(self.logits(feat)).unsqueeze(2) * cv
@@ -675,8 +631,7 @@ class CostVolumeDisparityAttention(nn.Module):
         self.pos_embed0 = PositionalEmbedding(d_model, max_len=max_len)
 
     def _fast(self, cv, window_size=(-1, -1)) -> bool:
-        if not (DT_FAST and cv.is_cuda and cv.dtype in HIP_DTYPES and not torch.is_grad_enabled()
-                and window_size == (-1, -1)) or self.training:
+        if not (DT_FAST and _hip(cv) and window_size == (-1, -1)) or self.training:
             return False
         a = self.sa[0].self_attn if len(self.sa) else None
         return (a is not None and cv.shape[1] == 28 and a.num_heads == 4 and self.sa[0].linear1.out_features == 28
@@ -685,14 +640,8 @@ class CostVolumeDisparityAttention(nn.Module):
                                                    for m in self.sa))
 
     def _packed(self):
-        ts = [t for m in self.sa for t in m.parameters()]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
-        hit = self.__dict__.get("_fsmi_pack")
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, ops.pack_dt_layers(list(self.sa)))
-            self.__dict__["_fsmi_pack"] = hit
-        return hit[1]
+        return _cached(self, "_fsmi_pack", [t for m in self.sa for t in m.parameters()],
+                       lambda: ops.pack_dt_layers(list(self.sa)))
 
     def forward(self, cv, window_size=(-1, -1)):
         B, C, D, H, W = cv.shape

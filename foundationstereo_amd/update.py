@@ -7,9 +7,10 @@ the reference's cats done as zero-copy input segments and bias / ReLU / GELU /
 layer-scale / residual / 0.25-scale fused into the epilogue.  Weights are
 packed once per (module, weight version).  The gates between the convs --
 sigmoid of z/r, ``r*h``, ``cat([r*h, x])``, ``tanh``, ``(1-z)h + zq`` and the
-``small*att + large*(1-att)`` selection -- are two fused kernels per
-SelectiveConvGRU (``ops.gru_reset``, ``ops.gru_blend``); ``convz`` and
-``convr`` run as ONE conv with stacked weights.  The two 7x7 convs run on their
+``small*att + large*(1-att)`` selection -- run in the epilogues of the gate convs
+(``ops.conv2d_gate``); ``convz`` and ``convr`` run as ONE conv with stacked
+weights.  ``RaftConvGRU`` on its own and the torch path keep the two gate kernels
+``ops.gru_reset`` / ``ops.gru_blend``.  The two 7x7 convs run on their
 own kernels: ``convd1`` (1 -> 64, + ReLU) on ``ops.conv2d_1in``, the depthwise
 ``dwconv`` on ``ops.dwconv2d``; ``pool2x`` is ``ops.pool2x`` and ``interp``
 ``ops.resize_bilinear``.  Under the reference's autocast the same HIP path runs
@@ -18,44 +19,40 @@ torch path (``CONV_ENGINE = "miopen"`` forces it, for A/B).
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .submodule import HIP_DTYPES, EdgeNextConvEncoder, _f32
+from .submodule import EdgeNextConvEncoder, _cached, _f32, _hip
 
-import os
-
+# What still switches a path here, and who uses it:
+#   CONV_ENGINE     "miopen" forces the torch path (bench.py --conv-engine)
+#   OVERLAP         side streams for the motion path, the GRU small branches, the mask head and the gru16 /
+#                   gru08 pipeline (FSMI_OVERLAP; bench.py)
+#   PIPE_BRANCH     run_pipelined: gru04's small branch on its own stream (FSMI_PIPE_BRANCH;
+#                   tests/test_gpu_capture_fork.py)
+#   MOTION_ON_MAIN  run_pipelined: the motion path (lookup + encoder) on the main stream instead of the
+#                   motion stream (FSMI_MOTION_ON_MAIN; tests/test_gpu_capture_fork.py)
+#   CTX_PRE         SelectiveConvGRU.conv0's context segment convolved once per forward (context_pre);
+#                   False: every iteration (tests/test_gpu_ctx_pre.py, test_gpu_range.py set the attribute)
+#   COUT1           DispHead's last conv (128 -> 1) on its own fp32 kernel (ops.conv3x3_cout1); False: the
+#                   halo conv tile (tests/test_gpu_ctx_pre.py sets the attribute)
 CONV_ENGINE = "fsmi"
-# A/B knobs (default on): motion path on a side stream; GRU gates in the conv epilogues
 OVERLAP = os.environ.get("FSMI_OVERLAP", "1") != "0"
-FUSED_GATES = os.environ.get("FSMI_FUSED_GATES", "1") != "0"
-# gru16 / gru08 pipelined one iteration ahead (BasicSelectiveMultiUpdateBlock.run_pipelined);
-# PIPE_BRANCH: gru04's small branch on its own stream there
-PIPELINE = os.environ.get("FSMI_PIPELINE", "1") != "0"
 PIPE_BRANCH = os.environ.get("FSMI_PIPE_BRANCH", "1") != "0"
-# run_pipelined: the motion path (lookup + encoder) on the main stream -- it is on the iteration's
-# critical chain between head(t-1) and gru04(t), both on main, with nothing beside it on main -- instead
-# of the motion stream (two cross-stream edges per iteration on that chain); A/B knob
 MOTION_ON_MAIN = os.environ.get("FSMI_MOTION_ON_MAIN", "0") != "0"
-
-
-# SelectiveConvGRU.conv0's context segment convolved once per forward (context_pre); 0: every iteration
-CTX_PRE = os.environ.get("FSMI_CTX_PRE", "1") != "0"
-# DispHead's last conv (128 -> 1) on its own fp32 kernel (ops.conv3x3_cout1); 0: the halo conv tile
-COUT1 = os.environ.get("FSMI_COUT1", "1") != "0"
-# the disparity head writes disp + delta into the next encoder buffer (A/B knob)
-HEAD_INPLACE = os.environ.get("FSMI_HEAD_INPLACE", "1") != "0"
-_CONVD1_MIOPEN = os.environ.get("FSMI_CONVD1_MIOPEN", "0") == "1"
-_POOL_TORCH = os.environ.get("FSMI_POOL_TORCH", "0") == "1"        # A/B knob: torch avg_pool2d
+CTX_PRE = True
+COUT1 = True
 
 
 def _fast(x) -> bool:
     """The HIP path applies: ROCm tensor, no grad.  Under the reference's autocast
     (scripts/run_demo.py:161) fp16 / bf16 inputs are cast up and the loop still runs on the HIP
     kernels in fp32."""
-    return CONV_ENGINE == "fsmi" and x.is_cuda and x.dtype in HIP_DTYPES and not torch.is_grad_enabled()
+    return CONV_ENGINE == "fsmi" and _hip(x)
 
 
 def _f32s(xs):
@@ -66,32 +63,25 @@ def _packed(*mods, cin_order=None):
     """Halo-kernel weights of one Conv2d/Linear (or several stacked along Cout),
     cached on the first module and rebuilt when any weight/bias changes.  ``cin_order``: input
     channels packed in this order (the caller passes its segments in the same order); a subset of
-    the input channels packs the conv restricted to them (one cache entry per order)."""
-    key = tuple((id(m), m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version)
-                for m in mods) + (tuple(cin_order) if cin_order is not None else None,)
-    if cin_order is None:
-        slot, d = "_fsmi_pack", mods[0].__dict__
-    else:
-        slot, d = tuple(cin_order), mods[0].__dict__.setdefault("_fsmi_pack_perm", {})
-    hit = d.get(slot)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            ws = [m.weight if m.weight.dim() == 4 else m.weight[:, :, None, None] for m in mods]
-            if cin_order is not None:
-                # runs of consecutive channels as slices: no index tensor to upload (a pack first built
-                # under a stream capture must not copy from the host)
-                runs = []
-                for c in cin_order:
-                    if runs and c == runs[-1][1]:
-                        runs[-1][1] = c + 1
-                    else:
-                        runs.append([c, c + 1])
-                ws = [torch.cat([w[:, a:b] for a, b in runs], 1) for w in ws]
-            pk = ops.PackedConv(*ws, mode="halo")
-            bias = torch.cat([m.bias.detach().float() for m in mods]).contiguous()
-        hit = (key, pk, bias)
-        d[slot] = hit
-    return hit[1], hit[2]
+    the input channels packs the conv restricted to them (one cache slot per order)."""
+    def build():
+        ws = [m.weight if m.weight.dim() == 4 else m.weight[:, :, None, None] for m in mods]
+        if cin_order is not None:
+            # runs of consecutive channels as slices: no index tensor to upload (a pack first built
+            # under a stream capture must not copy from the host)
+            runs = []
+            for c in cin_order:
+                if runs and c == runs[-1][1]:
+                    runs[-1][1] = c + 1
+                else:
+                    runs.append([c, c + 1])
+            ws = [torch.cat([w[:, a:b] for a, b in runs], 1) for w in ws]
+        pk = ops.PackedConv(*ws, mode="halo")
+        bias = torch.cat([m.bias.detach().float() for m in mods]).contiguous()
+        return pk, bias
+
+    slot = "_fsmi_pack" if cin_order is None else f"_fsmi_pack_{tuple(cin_order)}"
+    return _cached(mods[0], slot, [t for m in mods for t in (m.weight, m.bias)], build)
 
 
 _SIDE = {}
@@ -179,11 +169,6 @@ def stream_wait(waiter, waited):
 # side stream the SelectiveConvGRU small branch forks to (1); 0: the branches run in order on the
 # caller's stream (run_pipelined: the pipeline stream is itself a side stream, see capture_fork)
 _BRANCH = [1]
-# run_pipelined: gru08(t+1)'s interp(gru16(t+1)) enqueued right after gru16(t+1), beside gru04(t)
-# (FSMI_EARLY_INTERP=0: after gru04(t), as the reference orders it)
-EARLY_INTERP = os.environ.get("FSMI_EARLY_INTERP", "1") != "0"
-# DispHead's EdgeNeXt MLPs as one fused kernel (ops.edgenext_mlp); FSMI_FUSED_MLP=0: the two 1x1 convs
-_FUSED_MLP = os.environ.get("FSMI_FUSED_MLP", "1") != "0"
 
 
 def _branch_stream(device):
@@ -220,7 +205,7 @@ class DispHead(nn.Module):
         y = _conv(self.conv[0], [_f32(x)], "relu")
         for enc in (self.conv[2], self.conv[3]):
             d = ops.dwconv2d(y, enc.dwconv.weight, enc.dwconv.bias)   # depthwise 7x7; norm=None
-            if _FUSED_MLP and enc.pwconv1.out_features == 4 * enc.pwconv1.in_features == 512:
+            if enc.pwconv1.out_features == 4 * enc.pwconv1.in_features == 512:
                 # x + gamma * pw2(gelu(pw1(.))) in one kernel: the 4C GELU map stays in LDS
                 pk1, b1 = _packed(enc.pwconv1)
                 pk2, b2 = _packed(enc.pwconv2)
@@ -280,10 +265,7 @@ class BasicMotionEncoder(nn.Module):
         return self.encode_into(disp, geo_fn(disp), out)
 
     def _disp_feat(self, disp, out=None):
-        if _CONVD1_MIOPEN:                                     # A/B knob: the MIOpen conv + ReLU
-            d = F.relu_(self.convd1(disp))
-        else:
-            d = ops.conv2d_1in(disp, self.convd1.weight, self.convd1.bias, relu=True)   # 7x7, 1 -> 64
+        d = ops.conv2d_1in(disp, self.convd1.weight, self.convd1.bias, relu=True)   # 7x7, 1 -> 64
         return _conv(self.convd2, [d], "relu", out=out)
 
     def _encode_rest(self, disp, c1, out):
@@ -311,7 +293,7 @@ class BasicMotionEncoder(nn.Module):
 
 
 def pool2x(x):
-    if _fast(x) and not _POOL_TORCH:
+    if _fast(x):
         return ops.pool2x(_f32(x))
     return F.avg_pool2d(x, 3, stride=2, padding=1)
 
@@ -326,16 +308,11 @@ def interp(x, dest):
     return F.interpolate(x, dest.shape[2:], mode="bilinear", align_corners=True)
 
 
-def _stacked_zr(gru, cache):
+def _stacked_zr(gru):
     """[convz; convr] weights stacked along out-channels (cached per weight version)."""
     wz, wr, bz, br = gru.convz.weight, gru.convr.weight, gru.convz.bias, gru.convr.bias
-    key = tuple((t.data_ptr(), t._version) for t in (wz, wr, bz, br))
-    hit = cache.get(id(gru))
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            hit = (key, torch.cat([wz, wr], 0).contiguous(), torch.cat([bz, br], 0).contiguous())
-        cache[id(gru)] = hit
-    return hit[1], hit[2]
+    return _cached(gru, "_fsmi_zr", [wz, wr, bz, br],
+                   lambda: (torch.cat([wz, wr], 0).contiguous(), torch.cat([bz, br], 0).contiguous()))
 
 
 class RaftConvGRU(nn.Module):
@@ -347,10 +324,9 @@ class RaftConvGRU(nn.Module):
         self.convz = nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=p)
         self.convr = nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=p)
         self.convq = nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel_size, padding=p)
-        self._zr_cache = {}
 
     def zr(self, hx):
-        w, b = _stacked_zr(self, self._zr_cache)
+        w, b = _stacked_zr(self)
         return F.conv2d(hx, w, b, padding=self.convz.padding)
 
     def zr_fast(self, hx):
@@ -426,13 +402,6 @@ class SelectiveConvGRU(nn.Module):
             hx = _conv(self.conv1[0], [xc, h], "relu")
             # gates in the conv epilogues: z / r*h from the stacked zr convs, then each convq reads
             # [r*h, x] as two segments and blends straight into the new state
-            if not FUSED_GATES:
-                zr_s = self.small_gru.zr_fast(hx)
-                zr_l = self.large_gru.zr_fast(hx)
-                qs_in, ql_in = ops.gru_reset(zr_s, zr_l, h, xc)
-                q_s = _conv(self.small_gru.convq, [qs_in])
-                q_l = _conv(self.large_gru.convq, [ql_in])
-                return ops.gru_blend(zr_s, zr_l, q_s, q_l, h, att.float())
             att = att.float().contiguous()
             out = torch.empty_like(h)
 
@@ -516,7 +485,7 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
     def context_pre(self, inp):
         """Per GRU level (gru04, gru08, gru16 as ``inp``), ``SelectiveConvGRU.context_pre`` of its context
         feature: the loop-invariant part of conv0, computed once per forward (HIP path; None otherwise or
-        with FSMI_CTX_PRE=0)."""
+        with ``update.CTX_PRE = False``)."""
         if not CTX_PRE or not inp or not _fast(inp[0]):
             return None
         grus = [self.gru04, getattr(self, "gru08", None), getattr(self, "gru16", None)]
@@ -592,12 +561,9 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
         # the disparity lives in the last channel of the encoder output it feeds: the disparity head
         # writes disp + delta straight into the next iteration's buffer (no cat copy, no add pass)
         enc = disp.new_empty(B, nc + 1, H, W)                                   # on main
-        if HEAD_INPLACE:
-            enc[:, nc:].copy_(disp)
-            disp = enc[:, nc:]
+        enc[:, nc:].copy_(disp)
+        disp = enc[:, nc:]
         for t in range(iters):
-            if not HEAD_INPLACE and t:
-                enc = disp.new_empty(B, nc + 1, H, W)
             if MOTION_ON_MAIN:
                 self.encoder.motion_into(disp, geo_fn, enc)
             else:
@@ -613,7 +579,7 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
                     n2 = self.gru16(att[2], n2, inp[2], pool2x(n1), pre=p2)
                     # gru08(t+1)'s upsampled gru16 input, also beside gru04(t): one kernel less between
                     # gru04(t) and gru08(t+1)
-                    up2 = interp(n2, n1) if EARLY_INTERP else None
+                    up2 = interp(n2, n1)
                 _BRANCH[0] = 1
             _BRANCH[0] = 1 if main_branch else 0
             n0 = self.gru04(att[0], n0, inp[0], enc, interp(n1, n0), pre=p0)
@@ -624,7 +590,7 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
                 # stream waiting on the pipeline stream and waited on by it (capture_fork)
                 _BRANCH[0] = 0
                 with torch.cuda.stream(s_gru):           # gru08(t+1), beside the heads + motion(t+1)
-                    n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), up2 if EARLY_INTERP else interp(n2, n1), pre=p1)
+                    n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), up2, pre=p1)
                 _BRANCH[0] = 1
             if t + 1 == iters:
                 # test mode upsamples only the last iteration's disparity: the reference computes the
@@ -632,14 +598,12 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
                 stream_wait(s_mot, main)
                 with torch.cuda.stream(s_mot):
                     mask = _conv(self.mask[2], [_conv(self.mask[0], [n0], "relu")], "relu", alpha=0.25)
-            if t + 1 < iters and HEAD_INPLACE:
+            if t + 1 < iters:
                 enc = disp.new_empty(B, nc + 1, H, W)
                 self.disp_head(n0, res=disp, out=enc, co0=nc)
                 disp = enc[:, nc:]
-            elif HEAD_INPLACE:
-                disp = self.disp_head(n0, res=disp)
             else:
-                disp = disp + self.disp_head(n0).float()
+                disp = self.disp_head(n0, res=disp)
             if not MOTION_ON_MAIN or t + 1 == iters:
                 stream_wait(main, s_mot)
         stream_wait(main, s_gru)
