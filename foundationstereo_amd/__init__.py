@@ -4,7 +4,9 @@ Hand-written gfx950 HIP kernels (``csrc/``, C ABI in ``include/fsmi.h``,
 loaded via ctypes from ``_lib/libfsmi.so``) behind the reference's own module
 and function API (``submodule``, ``geometry``, ``update``, ``utils``,
 ``foundation_stereo``, and the backbone ``backbone.Feature``), plus ``cloud``:
-depth, XYZ map and denoised point cloud from the disparity.  See DESIGN.md.
+depth, XYZ map and denoised point cloud from the disparity, ``frames``: camera
+frames to model input and the disparity picture, and ``demo``: the reference's
+demo end to end (``python -m foundationstereo_amd.demo``).  See DESIGN.md.
 """
 import os as _os
 

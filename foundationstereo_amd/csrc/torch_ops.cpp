@@ -13,14 +13,17 @@
 //   context_upsample    core/submodule.py:456-468      softmax_context_upsample core/foundation_stereo.py:187-189
 //   disp_to_xyz         scripts/run_demo.py:173-251, Utils.py:56-75
 //   radius_outlier_mask scripts/run_demo.py:270-273 (Open3D remove_radius_outlier)
+//   frames_ingest       scripts/run_demo.py:131-159   vis_disparity     Utils.py:108-133
 #include <torch/library.h>
 #include <ATen/core/Tensor.h>
 #include <ATen/ops/empty.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cmath>
 #include <cstdint>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/fsmi.h"
@@ -258,6 +261,75 @@ Tensor radius_outlier_mask(const Tensor& points_, const c10::optional<Tensor>& v
   return keep.view(at::kBool);
 }
 
+void check_u8(const char* name, const Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), name, ": fsmi ops run on ROCm (HIP) device tensors only; got ", t.device());
+  TORCH_CHECK(t.scalar_type() == at::kByte, name, ": expected uint8, got ", t.scalar_type());
+}
+
+// cv2.resize's cvRound and Python's round(): to nearest, ties to even (the default rounding mode)
+int64_t round_half_even(double v) { return static_cast<int64_t>(std::nearbyint(v)); }
+
+// InputPadder(mode='sintel', divis_by), core/utils/utils.py:26-29,35: (before, after) of one axis
+std::pair<int64_t, int64_t> sintel_pad(int64_t n, int64_t d) {
+  const int64_t pad = (((n / d) + 1) * d - n) % d;
+  return {pad / 2, pad - pad / 2};
+}
+
+std::tuple<Tensor, Tensor> frames_ingest(const Tensor& left_, const Tensor& right_, double scale, int64_t divis_by) {
+  const c10::DeviceGuard guard(left_.device());
+  check_u8("frames_ingest", left_); check_u8("frames_ingest", right_);
+  TORCH_CHECK(left_.dim() == 4 && left_.sizes() == right_.sizes() && left_.device() == right_.device(),
+              "frames_ingest: left, right must be (B,H,W,C) alike on one device");
+  TORCH_CHECK(divis_by > 0, "frames_ingest: divis_by must be positive");
+  TORCH_CHECK(scale > 0.0 && scale <= 1.0, "frames_ingest: scale must be in (0, 1]");
+  Tensor left = left_.contiguous(), right = right_.contiguous();
+  const int64_t B = left.size(0), H = left.size(1), W = left.size(2), C = left.size(3);
+  const int64_t Hs = scale == 1.0 ? H : round_half_even(H * scale), Ws = scale == 1.0 ? W : round_half_even(W * scale);
+  const auto [pt, pb] = sintel_pad(Hs, divis_by);
+  const auto [pl, pr] = sintel_pad(Ws, divis_by);
+  Tensor batch = at::empty({B, 2, 3, Hs + pt + pb, Ws + pl + pr}, left.options().dtype(at::kFloat));
+  Tensor u8 = at::empty({B, Hs, Ws, 3}, left.options());
+  ok(fsmi_frames_ingest(left.data_ptr<uint8_t>(), right.data_ptr<uint8_t>(), mp(batch), u8.data_ptr<uint8_t>(), B, H,
+                        W, C, scale, Hs, Ws, pl, pr, pt, pb, divis_by, stream_of(left)),
+     "frames_ingest");
+  return {batch, u8};
+}
+
+// min / max (computed, or the caller's explicit values) then the picture: frames.vis_disparity
+std::tuple<Tensor, Tensor> vis_disparity(const Tensor& disp_, const Tensor& lut_, c10::optional<double> min_val,
+                                         c10::optional<double> max_val, c10::optional<double> invalid_thres_,
+                                         const c10::optional<Tensor>& image_) {
+  const c10::DeviceGuard guard(disp_.device());
+  const float invalid_thres = invalid_thres_.has_value() ? (float)*invalid_thres_ : INFINITY;
+  check_dev("vis_disparity", disp_);
+  check_u8("vis_disparity", lut_);
+  TORCH_CHECK(disp_.dim() == 3, "vis_disparity: disp must be (B,H,W)");
+  TORCH_CHECK(lut_.dim() == 2 && lut_.size(0) == 256 && lut_.size(1) == 3 && lut_.device() == disp_.device(),
+              "vis_disparity: lut must be uint8 (256,3) on the device of disp");
+  Tensor disp = dense(disp_), lut = lut_.contiguous();
+  const int64_t B = disp.size(0), H = disp.size(1), W = disp.size(2);
+  Tensor image;
+  if (image_.has_value() && image_->defined()) {
+    check_u8("vis_disparity", *image_);
+    TORCH_CHECK(image_->device() == disp.device() && image_->dim() == 4 && image_->size(0) == B &&
+                    image_->size(1) == H && image_->size(2) == W && image_->size(3) == 3,
+                "vis_disparity: image must be uint8 (B,H,W,3) on the device of disp");
+    image = image_->contiguous();
+  }
+  void* s = stream_of(disp);
+  Tensor minmax = at::empty({B, 2}, disp.options());
+  if (!(min_val.has_value() && max_val.has_value()))
+    ok(fsmi_disp_minmax(cp(disp), mp(minmax), B, H, W, (float)invalid_thres, s), "disp_minmax");
+  if (min_val.has_value()) minmax.select(1, 0).fill_(*min_val);
+  if (max_val.has_value()) minmax.select(1, 1).fill_(*max_val);
+  Tensor out = at::empty({B, H, image.defined() ? 2 * W : W, 3}, lut.options());
+  ok(fsmi_disp_colorize(cp(disp), cp(minmax), lut.data_ptr<uint8_t>(),
+                        image.defined() ? image.data_ptr<uint8_t>() : nullptr, out.data_ptr<uint8_t>(), B, H, W,
+                        (float)invalid_thres, s),
+     "disp_colorize");
+  return {out, minmax};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(fsmi, m) {
@@ -276,6 +348,11 @@ TORCH_LIBRARY(fsmi, m) {
   m.def("disp_to_xyz(Tensor disp, float fx, float fy, float cx, float cy, float baseline, float zmin=0.1, "
         "float z_far=10.0, bool remove_invisible=True, int camera_type=0) -> (Tensor, Tensor, Tensor)");
   m.def("radius_outlier_mask(Tensor points, Tensor? valid=None, int nb_points=30, float radius=0.03) -> Tensor");
+  // around the forward (scripts/run_demo.py:131-170): (batch, image_u8) and (picture, minmax)
+  m.def("frames_ingest(Tensor left, Tensor right, float scale=1.0, int divis_by=32) -> (Tensor, Tensor)");
+  // invalid_thres=None is +inf, the reference's default (the schema grammar has no literal for it)
+  m.def("vis_disparity(Tensor disp, Tensor lut, float? min_val=None, float? max_val=None, float? invalid_thres=None, "
+        "Tensor? image=None) -> (Tensor, Tensor)");
 }
 
 // ROCm builds of PyTorch expose HIP devices under the CUDA dispatch key
@@ -292,4 +369,6 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("softmax_context_upsample", softmax_context_upsample);
   m.impl("disp_to_xyz", disp_to_xyz);
   m.impl("radius_outlier_mask", radius_outlier_mask);
+  m.impl("frames_ingest", frames_ingest);
+  m.impl("vis_disparity", vis_disparity);
 }

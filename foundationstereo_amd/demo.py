@@ -1,0 +1,147 @@
+"""The reference's demo (scripts/run_demo.py) end to end on the device.
+
+    python -m foundationstereo_amd.demo --left_file left.png --right_file right.png \\
+        --intrinsic_file K.txt --ckpt_dir pretrained_models/model_best_bp2.pth --out_dir out
+
+Frames in (``frames.ingest``), forward, picture (``frames.vis_disparity``), depth and clouds
+(``cloud.disparity_to_cloud``): the disparity never returns to the host between them.  Writes
+``vis.png``, ``depth_meter.npy`` (pinhole only), ``cloud.ply`` and ``cloud_denoise.ply`` into
+``--out_dir`` next to copies of the inputs, and prints one JSON line.  The flags carry the reference's
+names and defaults (run_demo.py:45-80); ``--out_dir`` is honoured (the reference replaces it with a
+timestamped folder) and no viewer window opens.  ``--synthetic`` runs without a checkpoint on the
+hash-initialised model the tests use.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import shutil
+import sys
+
+import numpy as np
+import torch
+
+from . import cloud, frames
+
+
+def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid_iters=32, camera_type="pinhole",
+             z_far=10.0, remove_invisible=1, denoise_cloud=1, denoise_nb_points=30, denoise_radius=0.03,
+             get_pc=1) -> dict:
+    """scripts/run_demo.py:131-275 for one pair of uint8 frames (arrays or device tensors).  Returns
+    device tensors: ``disp`` (H,W), ``vis`` (H,2W,3) uint8, ``minmax`` (2), ``depth`` (H,W), ``cloud`` and
+    ``cloud_denoise`` as (points (M,3), colors (M,3) uint8) -- the last three None without ``get_pc``,
+    ``cloud_denoise`` None without ``denoise_cloud`` -- and ``frames``, the ingest result."""
+    fr = frames.ingest(left_u8, right_u8, scale=scale)
+    if len(fr.batch) != 1:
+        raise ValueError(f"run_pair: one pair at a time, got a batch of {len(fr.batch)}")
+    with torch.no_grad():
+        if not hiera:
+            disp = model.forward(fr.left, fr.right, iters=valid_iters, test_mode=True)
+        else:
+            disp = model.run_hierachical(fr.left, fr.right, iters=valid_iters, test_mode=True, small_ratio=0.5)
+    disp = fr.padder.unpad(disp.float())                                    # run_demo.py:166
+    other = {}
+    vis = frames.vis_disparity(disp[:, 0], image=fr.image_u8, other_output=other)
+    out = {"disp": disp[0, 0], "vis": vis[0], "minmax": other["minmax"][0], "frames": fr,
+           "depth": None, "cloud": None, "cloud_denoise": None}
+    if get_pc:
+        c = cloud.disparity_to_cloud(disp, K, baseline, image=fr.image_u8, denoise=bool(denoise_cloud),
+                                     nb_points=denoise_nb_points, radius=denoise_radius, scale=scale,
+                                     camera_type=camera_type, remove_invisible=bool(remove_invisible), z_far=z_far)[0]
+        out["depth"] = c.depth
+        out["cloud"] = (c.xyz_map[c.valid], fr.image_u8[0][c.valid])
+        if denoise_cloud:
+            out["cloud_denoise"] = (c.points, c.colors)
+    return out
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m foundationstereo_amd.demo",
+                                description="FoundationStereo demo: stereo pair -> disparity picture, depth, point clouds")
+    p.add_argument("--left_file", default="assets/left.png", type=str, help="Path to the left image (.npy or an image file)")
+    p.add_argument("--right_file", default="assets/right.png", type=str, help="Path to the right image")
+    p.add_argument("--intrinsic_file", default="assets/K.txt", type=str,
+                   help="Path to camera intrinsic matrix and baseline file")
+    p.add_argument("--ckpt_dir", default="pretrained_models/model_best_bp2.pth", type=str, help="Path to pretrained model")
+    p.add_argument("--out_dir", default="output/", type=str, help="Directory to save results")
+    p.add_argument("--camera_type", type=str, default="pinhole", choices=["pinhole", "panorama"],
+                   help="Type of camera: pinhole (standard perspective) or panorama (equirectangular projection)")
+    p.add_argument("--scale", default=1, type=float, help="Downsize the image by scale, must be <=1")
+    p.add_argument("--hiera", default=0, type=int,
+                   help="Use hierarchical inference (only needed for high-resolution images (>1K))")
+    p.add_argument("--z_far", default=10, type=float, help="Maximum depth to clip in point cloud")
+    p.add_argument("--valid_iters", type=int, default=32, help="Number of flow-field updates during forward pass")
+    p.add_argument("--get_pc", type=int, default=1, help="Save point cloud output")
+    p.add_argument("--remove_invisible", default=1, type=int,
+                   help="Remove non-overlapping observations between left and right images from point cloud")
+    p.add_argument("--denoise_cloud", type=int, default=1, help="Whether to denoise the point cloud")
+    p.add_argument("--denoise_nb_points", type=int, default=30,
+                   help="Number of points to consider for radius outlier removal")
+    p.add_argument("--denoise_radius", type=float, default=0.03, help="Radius to use for outlier removal")
+    p.add_argument("--synthetic", action="store_true",
+                   help="No checkpoint: the hash-initialised model of the tests (synth.make_args + synth.init_module_)")
+    p.add_argument("--max_disp", type=int, default=192, help="With --synthetic: the model's max_disp")
+    p.add_argument("--vit_size", type=str, default="vits", choices=["vits", "vitb", "vitl"],
+                   help="With --synthetic: the backbone size")
+    p.add_argument("--backbone", type=str, default="synthetic", choices=["synthetic", "real"],
+                   help="real: the EdgeNeXt + DepthAnythingV2 backbone on HIP; synthetic: the seeded stand-in features")
+    return p
+
+
+def load_model(a, device):
+    if a.synthetic:
+        from . import synth
+        from .foundation_stereo import FoundationStereo
+        args = synth.make_args(max_disp=a.max_disp, vit_size=a.vit_size)
+        args["backbone"] = a.backbone
+        model = FoundationStereo(args).eval()
+        synth.init_module_(model, seed=1234)
+        return model.to(device)
+    from . import checkpoint
+    over = {k: v for k, v in vars(a).items() if k not in ("synthetic", "max_disp", "vit_size", "backbone")}
+    model, _ = checkpoint.load_model(a.ckpt_dir, over, device=device, backbone=a.backbone == "real")   # run_demo.py:111-128
+    return model
+
+
+def main(argv=None) -> dict:
+    a = parser().parse_args(argv)
+    if not 0 < a.scale <= 1:
+        raise SystemExit("scale must be in (0, 1]")                           # run_demo.py:149
+    if not torch.cuda.is_available():
+        raise SystemExit("demo: needs a HIP device")
+    device = torch.device("cuda", torch.cuda.current_device())
+    os.makedirs(a.out_dir, exist_ok=True)
+    for src, stem in ((a.left_file, "left"), (a.right_file, "right"), (a.intrinsic_file, "K")):   # run_demo.py:106-108
+        shutil.copy(src, os.path.join(a.out_dir, stem + os.path.splitext(src)[1]))
+    K, baseline = cloud.read_intrinsics(a.intrinsic_file)
+    model = load_model(a, device)
+    left, right = frames.read_image(a.left_file), frames.read_image(a.right_file)
+    out = run_pair(model, left, right, K, baseline, scale=a.scale, hiera=a.hiera, valid_iters=a.valid_iters,
+                   camera_type=a.camera_type, z_far=a.z_far, remove_invisible=a.remove_invisible,
+                   denoise_cloud=a.denoise_cloud, denoise_nb_points=a.denoise_nb_points,
+                   denoise_radius=a.denoise_radius, get_pc=a.get_pc)
+    fr = out["frames"]
+    res = {"out_dir": a.out_dir, "image_size": list(out["disp"].shape), "padded_size": list(fr.batch.shape[-2:]),
+           "min_disp": float(out["minmax"][0]), "max_disp": float(out["minmax"][1])}
+
+    def path(name):
+        return os.path.join(a.out_dir, name)
+    frames.write_png(path("vis.png"), out["vis"])                             # run_demo.py:168-170
+    res["vis"] = path("vis.png")
+    if a.get_pc:
+        cloud.write_ply(path("cloud.ply"), *out["cloud"])                     # run_demo.py:255
+        res["cloud"], res["cloud_points"] = path("cloud.ply"), int(out["cloud"][0].shape[0])
+        if a.camera_type == "pinhole":
+            np.save(path("depth_meter.npy"), out["depth"].cpu().numpy())       # run_demo.py:259-261
+            res["depth"] = path("depth_meter.npy")
+        if a.denoise_cloud:
+            cloud.write_ply(path("cloud_denoise.ply"), *out["cloud_denoise"])  # run_demo.py:270-274
+            res["cloud_denoise"] = path("cloud_denoise.ply")
+            res["cloud_denoise_points"] = int(out["cloud_denoise"][0].shape[0])
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

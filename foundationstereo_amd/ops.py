@@ -1253,3 +1253,75 @@ def radius_outlier_mask(points: Tensor, valid: Tensor = None, nb_points: int = 3
     _lib.check(lib.fsmi_radius_count(_p(skeys), _p(perm), _p(pts4), _p(keep), N, float(radius), int(nb_points), s),
                "radius_count")
     return keep.view(torch.bool)
+
+
+# ---------------------------------------------------------------- frames in, pictures out
+
+def _check_u8(name: str, *ts: Tensor):
+    """``_check`` for the uint8 tensors of the frame / picture ops (frames, LUT, side-by-side image)."""
+    for t in ts:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected tensors")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: fsmi ops run on ROCm (HIP) device tensors only; got {t.device}")
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"{name}: expected uint8, got {t.dtype}")
+
+
+def frames_ingest(left: Tensor, right: Tensor, scale: float = 1.0, divis_by: int = 32, want_u8: bool = True):
+    """scripts/run_demo.py:131-159 in one launch.  left, right: uint8 (B,H,W,C), C in {1,3,4} ->
+    (batch fp32 (B,2,3,Hp,Wp) with [left, right] per pair, image_u8 (B,Hs,Ws,3) or None): resize by
+    ``scale`` (bilinear, half-pixel centres), gray -> 3 channels / alpha dropped, HWC -> CHW, replicate
+    padding to multiples of ``divis_by`` (InputPadder, sintel mode).  include/fsmi.h has the arithmetic."""
+    from .utils import InputPadder
+    _check_u8("frames_ingest", left, right)
+    if left.dim() != 4 or left.shape != right.shape or left.device != right.device:
+        raise RuntimeError(f"frames_ingest: left, right must be (B,H,W,C) alike on one device, got "
+                           f"{tuple(left.shape)} and {tuple(right.shape)}")
+    B, H, W, C = left.shape
+    scale = float(scale)
+    Hs, Ws = (H, W) if scale == 1.0 else (round(H * scale), round(W * scale))
+    pl, pr, pt, pb = InputPadder((Hs, Ws), divis_by=divis_by)._pad
+    left, right = left.contiguous(), right.contiguous()
+    batch = torch.empty((B, 2, 3, Hs + pt + pb, Ws + pl + pr), device=left.device, dtype=torch.float32)
+    u8 = torch.empty((B, Hs, Ws, 3), device=left.device, dtype=torch.uint8) if want_u8 else None
+    _lib.check(_lib.load().fsmi_frames_ingest(_p(left), _p(right), _p(batch), _p(u8) if want_u8 else None, B, H, W, C,
+                                              scale, Hs, Ws, pl, pr, pt, pb, int(divis_by), _stream(left)),
+               "frames_ingest")
+    return batch, u8
+
+
+def disp_minmax(disp: Tensor, invalid_thres: float = float("inf")) -> Tensor:
+    """Utils.py:115-123 per image: disp (B,H,W) -> (B,2) fp32 [min, max] over the pixels that are not
+    NaN and not >= invalid_thres; (+inf, -inf) for an image without one.  No host synchronisation."""
+    _check("disp_minmax", disp)
+    assert disp.dim() == 3, f"disp_minmax: disp must be (B,H,W), got {tuple(disp.shape)}"
+    B, H, W = disp.shape
+    disp = _c(disp)
+    minmax = torch.empty((B, 2), device=disp.device, dtype=torch.float32)
+    _lib.check(_lib.load().fsmi_disp_minmax(_p(disp), _p(minmax), B, H, W, float(invalid_thres), _stream(disp)),
+               "disp_minmax")
+    return minmax
+
+
+def disp_colorize(disp: Tensor, minmax: Tensor, lut: Tensor, invalid_thres: float = float("inf"),
+                  image: Tensor = None) -> Tensor:
+    """Utils.py:126-133: disp (B,H,W), minmax (B,2), lut uint8 (256,3) -> uint8 (B,H,W,3); with
+    ``image`` uint8 (B,H,W,3) -> (B,H,2W,3), the image left of the colours (run_demo.py:169)."""
+    _check("disp_colorize", disp, minmax)
+    _check_u8("disp_colorize", lut, *([] if image is None else [image]))
+    assert disp.dim() == 3, f"disp_colorize: disp must be (B,H,W), got {tuple(disp.shape)}"
+    B, H, W = disp.shape
+    if minmax.shape != (B, 2) or lut.shape != (256, 3):
+        raise RuntimeError(f"disp_colorize: minmax must be ({B},2) and lut (256,3), got {tuple(minmax.shape)} "
+                           f"and {tuple(lut.shape)}")
+    if image is not None and image.shape != (B, H, W, 3):
+        raise RuntimeError(f"disp_colorize: image must be ({B},{H},{W},3), got {tuple(image.shape)}")
+    if any(t.device != disp.device for t in (minmax, lut) + (() if image is None else (image,))):
+        raise RuntimeError("disp_colorize: all tensors must be on the device of disp")
+    disp, minmax, lut = _c(disp), minmax.contiguous(), lut.contiguous()
+    image = image.contiguous() if image is not None else None
+    out = torch.empty((B, H, 2 * W if image is not None else W, 3), device=disp.device, dtype=torch.uint8)
+    _lib.check(_lib.load().fsmi_disp_colorize(_p(disp), _p(minmax), _p(lut), _p(image) if image is not None else None,
+                                              _p(out), B, H, W, float(invalid_thres), _stream(disp)), "disp_colorize")
+    return out

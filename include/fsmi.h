@@ -411,6 +411,52 @@ int fsmi_cloud_cell_keys(const float* points, const unsigned char* valid, long l
 int fsmi_radius_count(const long long* sorted_keys, const long long* perm, const float* sorted_points4,
                       unsigned char* keep, int N, float radius, int nb_points, void* stream);
 
+/* ---- around the forward: frame ingest and the disparity picture -----------
+ * uint8 frames in, uint8 pictures out (with the cloud section, the exceptions to the all-fp32
+ * convention).  Nothing below synchronises the host; all of it can be captured in a hipGraph.
+ *
+ * Two camera frames to model input; replaces scripts/run_demo.py:131-159.  left, right: uint8
+ * (B,H,W,C), C = 1 (gray, replicated to three channels, :134-138), 3, or 4 (alpha dropped, :139-141).
+ * out: fp32 (B,2,3,Hp,Wp), [left, right] per pair, 16-byte aligned: the batch layout of
+ * dist.ShardedStereo / bench.py.  image_u8: NULL, or uint8 (B,Hs,Ws,3), the resized unpadded left
+ * frame (the reference's img0_ori).  One launch serves both frames of every pair.
+ * The HOST computes and passes in:
+ *   Hs, Ws   the resized size, round-half-even of H * scale and W * scale (cv2.resize(fx, fy,
+ *            dsize=None)'s cvRound; Python's round()); 0 < scale <= 1, and scale == 1 needs (Hs,Ws) == (H,W)
+ *   pads     InputPadder(mode='sintel', divis_by) of (Hs, Ws), core/utils/utils.py:26-29,35:
+ *            pad = (((n / d) + 1) d - n) % d, left / top get pad / 2, right / bottom the rest;
+ *            Hp = Hs + pad_top + pad_bottom and Wp likewise must be multiples of divis_by, Wp of 4 too
+ * The kernel computes, for padded pixel (yp, xp), the resized pixel
+ *   (ys, xs) = (clamp(yp - pad_top, 0, Hs-1), clamp(xp - pad_left, 0, Ws-1))           (replicate padding)
+ * and its value: scale == 1, the source byte (no arithmetic); otherwise cv2.INTER_LINEAR as it
+ * shrinks, half-pixel centres and no antialiasing:
+ *   sx = (xs + 0.5) / scale - 0.5 (fp64), x0 = floor(sx), wx = fp32(sx - x0), taps x0 and x0 + 1
+ *   clamped to [0, W-1]; rows likewise; in un-contracted fp32  top = a + (b - a) wx,  bot likewise,
+ *   v = top + (bot - top) wy;  result = clamp(floor(v + 0.5), 0, 255)  (half rounds up, as cv2's
+ *   fixed-point (sum + half) >> shift does on exact ties; an integer, as the reference resizes uint8)
+ * ImageNet normalisation is not applied here: it stays inside the forward, as in the reference. */
+int fsmi_frames_ingest(const unsigned char* left, const unsigned char* right, float* out, unsigned char* image_u8,
+                       int B, int H, int W, int C, double scale, int Hs, int Ws, int pad_left, int pad_right,
+                       int pad_top, int pad_bottom, int divis_by, void* stream);
+/* The picture of a disparity map; replaces vis_disparity, Utils.py:108-133 (run_demo.py:168-170).
+ * A pixel is VALID when it is not NaN and not >= invalid_thres (Utils.py:115; NaN is this library's
+ * definition: the reference's min() would return NaN and its uint8 cast is undefined).
+ * Step 1.  disp: (B,H,W), 16-byte aligned; minmax: (B,2) fp32.  The function itself sets minmax to
+ * (+inf, -inf) on the stream, then writes each image's min and max over its valid pixels
+ * (Utils.py:120-123); an image without a valid pixel keeps (+inf, -inf).  Exact and independent of
+ * the order in which blocks finish. */
+int fsmi_disp_minmax(const float* disp, float* minmax, int B, int H, int W, float invalid_thres, void* stream);
+/* Step 2.  minmax: (B,2) from step 1, or filled by the caller from explicit min_val / max_val;
+ * lut: uint8 (256,3) RGB on the device; image: NULL, or uint8 (B,H,W,3); out: uint8 (B,H,Wout,3),
+ * 4-byte aligned, Wout = 2W with an image (columns [0,W) the image, [W,2W) the colours: the demo's
+ * np.concatenate([img0_ori, vis], axis=1), run_demo.py:169), else W.  Per valid pixel, in fp32 with
+ * IEEE division and no contraction (Utils.py:126-130 with the table indexed directly):
+ *   t = clip((d - mn) / (mx - mn), 0, 1) * 255;  rgb = lut[(unsigned char) t]      (truncation)
+ * mx == mn maps every valid pixel to lut[0] (the reference divides by zero).  Invalid pixels are
+ * (0,0,0) (:131-132), so an image without a valid pixel is all zeros (:116-119). */
+int fsmi_disp_colorize(const float* disp, const float* minmax, const unsigned char* lut, const unsigned char* image,
+                       unsigned char* out, int B, int H, int W, float invalid_thres, void* stream);
+
 /* ---- live kernel timing (bench.py roofline) -----------------------------
  * When enabled, every launch of the kernels below is bracketed by a pair of
  * hipEvents recorded on the launch stream (skipped while the stream is being

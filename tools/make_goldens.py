@@ -271,12 +271,44 @@ def cloud():
     print("cloud_small", {k: (v.shape, v.dtype) for k, v in g.items()})
 
 
+def frames():
+    """vis_disparity (Utils.py:108-133) through its ``cmap=`` branch with matplotlib's turbo, and
+    InputPadder (core/utils/utils.py:17-41), run by the reference on a 37x53 case: pins
+    tests/frames_oracle.py and ``frames.TURBO``.  Needs matplotlib (here only, never in the package)."""
+    import_reference()
+    import importlib
+    import matplotlib
+    ref_utils = importlib.import_module("Utils")
+    ref_core_utils = importlib.import_module("core.utils.utils")
+    turbo = matplotlib.colormaps["turbo"]
+    H, W = 37, 53
+    disp = synth.uniform(synth.name_seed("frames_disp"), (H, W), 0.5, 60.0).astype(np.float32)
+    holes = np.argsort(synth.uniform(synth.name_seed("frames_holes"), (H * W,)))[:40]
+    disp.reshape(-1)[holes] = np.inf
+    g = {"disp": disp,
+         "lut": (turbo(np.arange(256, dtype=np.uint8))[:, :3] * 255).astype(np.uint8)}
+    other = {}
+    g["vis_auto"] = ref_utils.vis_disparity(disp, cmap=turbo, other_output=other)
+    g["minmax_auto"] = np.array([other["min_val"], other["max_val"]], dtype=np.float32)
+    g["vis_5_40"] = ref_utils.vis_disparity(disp, min_val=5, max_val=40, cmap=turbo, other_output={})
+    img = synth.uniform(synth.name_seed("frames_img"), (1, 3, H, W), 0.0, 255.0).astype(np.float32)
+    padder = ref_core_utils.InputPadder((H, W), divis_by=32, force_square=False)
+    g["pad_in"] = img
+    g["pad_out"] = padder.pad(t(img))[0].numpy()
+    g["pad"] = np.array(padder._pad)
+    assert g["pad"].tolist() == [5, 6, 13, 14] and g["vis_auto"].dtype == np.uint8
+    np.savez_compressed(os.path.join(OUT, "frames_small.npz"), **g)
+    print("frames_small", {k: (v.shape, v.dtype) for k, v in g.items()})
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud"]
+    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud", "frames"]
     if "cloud" in which:
         cloud()
-    if which == ["cloud"]:
+    if "frames" in which:
+        frames()
+    if set(which) <= {"cloud", "frames"}:
         return
     fs, sm, geo_mod, up_mod, ut = import_reference()
     if "backbone" in which:
