@@ -5,8 +5,10 @@ loaded via ctypes from ``_lib/libfsmi.so``) behind the reference's own module
 and function API (``submodule``, ``geometry``, ``update``, ``utils``,
 ``foundation_stereo``, and the backbone ``backbone.Feature``), plus ``cloud``:
 depth, XYZ map and denoised point cloud from the disparity, ``frames``: camera
-frames to model input and the disparity picture, and ``demo``: the reference's
-demo end to end (``python -m foundationstereo_amd.demo``).  See DESIGN.md.
+frames to model input and the disparity picture, ``demo``: the reference's
+demo end to end (``python -m foundationstereo_amd.demo``), and ``metrics``:
+EPE / RMSE / bad-pixel rates / D1 of a disparity against a ground truth
+(``python -m foundationstereo_amd.evaluate``).  See DESIGN.md.
 """
 import os as _os
 
@@ -22,6 +24,18 @@ _TUNING = _os.path.join(_os.path.dirname(_os.path.dirname(_os.path.abspath(__fil
 _os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
 if _os.path.isdir(_TUNING):
     _os.environ.setdefault("MIOPEN_USER_DB_PATH", _TUNING)
+
+
+_METRICS = ("stereo_metrics", "compute_stereo_metrics", "monitoring_stereo", "decode_gt", "MetricsAccumulator",
+            "StereoMetrics")
+
+
+def __getattr__(name):
+    # the scoring API at package level, resolved on first use (importing the package stays free of torch)
+    if name in _METRICS:
+        from . import metrics
+        return getattr(metrics, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def patch_reference(core_foundation_stereo_module):

@@ -75,6 +75,9 @@ SIGNATURES = {
     "fsmi_frames_ingest": [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _I, _I, _I, _P],
     "fsmi_disp_minmax": [_P, _P, _I, _I, _I, _F, _P],
     "fsmi_disp_colorize": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
+    "fsmi_disp_metrics_blocks": [_I, _I],
+    "fsmi_disp_metrics": [_P, _P, _P, _P, ctypes.POINTER(_F), _I, ctypes.c_double, _P, _P, _P, _P, _I, _I, _I, _P],
+    "fsmi_gt_decode": [_P, _P, _I, _I, _I, ctypes.c_double, _P],
     "fsmi_debug_conv_timestamps": [_P],
     "fsmi_range_status": [_I, ctypes.POINTER(_I)],
     "fsmi_set_range_safe": [_I],

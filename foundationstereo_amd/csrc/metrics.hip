@@ -1,0 +1,292 @@
+// How good is a disparity map: per-pair EPE, RMSE, bad-pixel rates and KITTI's D1 against a ground
+// truth, plus the prediction's own statistics (train/utils.py:88-141 compute_stereo_metrics and
+// train/losses.py:326-339 monitoring_stereo, which gather through a boolean mask, loop over the batch
+// in Python and synchronise the host 4 + K times per pair).  Here: one streaming pass and a tiny
+// second kernel, no host synchronisation, no allocation, capturable in a hipGraph.
+//   disp_metrics_partial   grid (NB, B): a block reduces its pixels of pair b into one row of 17 doubles
+//                          and STORES it (no float atomics: the order of every addition is fixed by
+//                          (H*W, NB) alone, so the same input gives the same bits on any device)
+//   disp_metrics_finalize  one block per pair: sums the NB rows in a fixed order, writes the raw
+//                          accumulators and the table of metrics
+//   gt_decode              the reference's 3 x uint8 ground-truth encoding (Utils.py:137-140) -> fp32
+// Per-pixel arithmetic is un-contracted fp32, as torch evaluates |pred - gt| > t on fp32 tensors; every
+// sum is fp64 ((double)e * (double)e is exact), counts are exact integers held as doubles.
+#include <climits>
+#include <cstdint>
+
+#include "fsmi_common.h"
+
+namespace fsmi {
+namespace {
+
+constexpr int NACC = FSMI_METRICS_NACC;
+constexpr int MAXT = FSMI_METRICS_MAX_THRESHOLDS;
+constexpr int kQuadsPerBlock = 1024;      // 256 lanes x 4 quads of 4 pixels
+constexpr int kMaxBlocks = 512;           // per pair; the finalize kernel reads at most 2 rows per lane
+
+static_assert(NACC == 9 + MAXT, "accumulator layout: 9 fixed slots then the thresholds");
+
+enum { A_N = 0, A_SE, A_SE2, A_D1, A_NONFINITE, A_SX, A_SX2, A_MIN, A_MAX, A_BAD };
+
+struct Metrics {
+  long long P;            // H * W
+  double gt_scale;
+  float thr[MAXT];        // unused slots +inf: e > +inf never counts
+};
+
+// min / max that propagate NaN (fminf / fmaxf return the other operand): once NaN, always NaN
+__device__ __forceinline__ double nan_min(double a, double b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
+__device__ __forceinline__ double combine(int slot, double a, double b) {
+  return slot == A_MIN ? nan_min(a, b) : slot == A_MAX ? nan_max(a, b) : a + b;
+}
+
+// The 256 lanes' rows of NACC values -> one row: lane s < NACC returns slot s (the others 0).  A
+// shuffle tree inside each wave, then waves 0..3 in index order: the order of the additions is a
+// function of the lane index alone.
+__device__ __forceinline__ double block_reduce(double (&v)[NACC], double (*lds)[NACC]) {
+#pragma unroll
+  for (int s = 0; s < NACC; ++s) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[s] = combine(s, v[s], __shfl_down(v[s], off, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int s = 0; s < NACC; ++s) lds[threadIdx.x >> 6][s] = v[s];
+  }
+  __syncthreads();
+  double r = 0.0;
+  if (threadIdx.x < NACC) {
+    const int s = threadIdx.x;
+    r = combine(s, combine(s, combine(s, lds[0][s], lds[1][s]), lds[2][s]), lds[3][s]);
+  }
+  return r;
+}
+
+__device__ __forceinline__ float decode_gt(unsigned r, unsigned g, unsigned b, double gt_scale) {
+  const int n = static_cast<int>(r * 65025u + g * 255u + b);          // <= 16 605 816
+  return static_cast<float>(static_cast<double>(n) / gt_scale);
+}
+
+// One lane's running row.  Counts stay below 2^32 per lane (a pair has at most 2^31 - 1 pixels).
+struct Lane {
+  double se = 0.0, se2 = 0.0, sx = 0.0, sx2 = 0.0;
+  unsigned n = 0, d1 = 0, nonfinite = 0, bad[MAXT] = {};
+  float mn = INFINITY, mx = -INFINITY;
+};
+
+// returns the error-map value of the pixel: e where valid, +inf where not
+__device__ __forceinline__ float take(Lane& a, float x, float gt, bool has_mask, unsigned char m, float x0,
+                                      const Metrics& g) {
+#pragma clang fp contract(off)
+  const double dx = static_cast<double>(x) - static_cast<double>(x0);
+  a.sx += dx;
+  a.sx2 += dx * dx;
+  a.mn = (x < a.mn || x != x) ? x : a.mn;
+  a.mx = (x > a.mx || x != x) ? x : a.mx;
+  const bool valid = has_mask ? m != 0 : (gt > 0.f && gt < INFINITY);
+  if (!valid) return INFINITY;
+  const float e = fabsf(x - gt);
+  const double ed = static_cast<double>(e);
+  a.n += 1;
+  a.se += ed;
+  a.se2 += ed * ed;
+  a.d1 += (e > 3.0f && e > __fmul_rn(0.05f, fabsf(gt))) ? 1u : 0u;
+  a.nonfinite += !(e < INFINITY) ? 1u : 0u;                          // NaN or inf
+#pragma unroll
+  for (int k = 0; k < MAXT; ++k) a.bad[k] += e > g.thr[k] ? 1u : 0u;   // NaN > t is false: "not bad"
+  return e;
+}
+
+// grid (NB, B); the blocks of one pair stride over its quads.  A pair starts at b * P pixels, which is
+// 16-byte aligned in the fp32 maps (4-byte in the mask, 12-byte quads in the u8 ground truth) only
+// when that is a multiple of 4: up to 3 head pixels and P' % 4 tail pixels are taken one by one by
+// block 0, everything between them as 4-wide groups that never leave the pair.
+template <bool U8GT>
+__global__ __launch_bounds__(256) void disp_metrics_partial_kernel(const float* __restrict__ pred,
+                                                                   const void* __restrict__ gt_any,
+                                                                   const unsigned char* __restrict__ mask,
+                                                                   double* __restrict__ partials,
+                                                                   float* __restrict__ error, Metrics g) {
+  __shared__ double lds[4][NACC];
+  const int b = blockIdx.y;
+  const long long P = g.P, start = b * P;
+  const float* p = pred + start;
+  const float* gtf = U8GT ? nullptr : static_cast<const float*>(gt_any) + start;
+  const unsigned char* gtu = U8GT ? static_cast<const unsigned char*>(gt_any) + 3 * start : nullptr;
+  const unsigned char* mk = mask ? mask + start : nullptr;
+  float* er = error ? error + start : nullptr;
+  const bool has_mask = mask != nullptr;
+  const float x0 = p[0];
+
+  const long long head = min(P, static_cast<long long>((4 - (start & 3)) & 3));
+  const long long nquad = (P - head) >> 2;
+  const long long tail = head + (nquad << 2);
+  const long long t = blockIdx.x * 256ll + threadIdx.x, stride = gridDim.x * 256ll;
+
+  Lane a;
+  auto one = [&](long long i) {                                      // pixel i of the pair, i < P
+    const float gt = U8GT ? decode_gt(gtu[3 * i], gtu[3 * i + 1], gtu[3 * i + 2], g.gt_scale) : gtf[i];
+    const float e = take(a, p[i], gt, has_mask, has_mask ? mk[i] : 0, x0, g);
+    if (er) er[i] = e;
+  };
+  if (t < head) one(t);
+  for (long long q = t; q < nquad; q += stride) {
+    const long long i = head + (q << 2);
+    const float4 x = *reinterpret_cast<const float4*>(p + i);
+    float gt[4];
+    if (U8GT) {
+      const uint3 w = *reinterpret_cast<const uint3*>(gtu + 3 * i);   // 12 bytes: r g b r | g b r g | b r g b
+      gt[0] = decode_gt(w.x & 255u, (w.x >> 8) & 255u, (w.x >> 16) & 255u, g.gt_scale);
+      gt[1] = decode_gt(w.x >> 24, w.y & 255u, (w.y >> 8) & 255u, g.gt_scale);
+      gt[2] = decode_gt((w.y >> 16) & 255u, w.y >> 24, w.z & 255u, g.gt_scale);
+      gt[3] = decode_gt((w.z >> 8) & 255u, (w.z >> 16) & 255u, w.z >> 24, g.gt_scale);
+    } else {
+      const float4 g4 = *reinterpret_cast<const float4*>(gtf + i);
+      gt[0] = g4.x; gt[1] = g4.y; gt[2] = g4.z; gt[3] = g4.w;
+    }
+    const unsigned m4 = has_mask ? *reinterpret_cast<const unsigned*>(mk + i) : 0u;
+    float4 e;
+    e.x = take(a, x.x, gt[0], has_mask, m4 & 255u, x0, g);
+    e.y = take(a, x.y, gt[1], has_mask, (m4 >> 8) & 255u, x0, g);
+    e.z = take(a, x.z, gt[2], has_mask, (m4 >> 16) & 255u, x0, g);
+    e.w = take(a, x.w, gt[3], has_mask, m4 >> 24, x0, g);
+    if (er) *reinterpret_cast<float4*>(er + i) = e;
+  }
+  if (tail + t < P) one(tail + t);
+
+  double v[NACC];
+  v[A_N] = a.n; v[A_SE] = a.se; v[A_SE2] = a.se2; v[A_D1] = a.d1; v[A_NONFINITE] = a.nonfinite;
+  v[A_SX] = a.sx; v[A_SX2] = a.sx2; v[A_MIN] = a.mn; v[A_MAX] = a.mx;
+#pragma unroll
+  for (int k = 0; k < MAXT; ++k) v[A_BAD + k] = a.bad[k];
+  const double r = block_reduce(v, lds);
+  if (threadIdx.x < NACC)
+    partials[(static_cast<long long>(b) * gridDim.x + blockIdx.x) * NACC + threadIdx.x] = r;
+}
+
+// One block per pair.  Lane t sums rows t, t + 256, ... (in index order) of the pair's NB partial
+// rows, then the same fixed tree as above.  Lane 0 turns the accumulators into the table.
+__global__ __launch_bounds__(256) void disp_metrics_finalize_kernel(const double* __restrict__ partials,
+                                                                    const float* __restrict__ pred,
+                                                                    double* __restrict__ sums,
+                                                                    double* __restrict__ table, int NB, long long P) {
+#pragma clang fp contract(off)
+  __shared__ double lds[4][NACC];
+  __shared__ double row[NACC];
+  const int b = blockIdx.x;
+  double v[NACC];
+#pragma unroll
+  for (int s = 0; s < NACC; ++s) v[s] = s == A_MIN ? INFINITY : s == A_MAX ? -INFINITY : 0.0;
+  for (int r = threadIdx.x; r < NB; r += 256) {
+    const double* src = partials + (static_cast<long long>(b) * NB + r) * NACC;
+#pragma unroll
+    for (int s = 0; s < NACC; ++s) v[s] = combine(s, v[s], src[s]);
+  }
+  const double r = block_reduce(v, lds);
+  if (threadIdx.x < NACC) {
+    sums[b * NACC + threadIdx.x] = r;
+    row[threadIdx.x] = r;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double* o = table + b * NACC;
+  const double n = row[A_N], Pd = static_cast<double>(P);
+  const bool any = n > 0.0;                                          // train/utils.py:122-123: an empty mask scores 0
+  o[0] = n;
+  o[1] = any ? row[A_SE] / n : 0.0;
+  o[2] = any ? sqrt(row[A_SE2] / n) : 0.0;
+  o[3] = any ? row[A_D1] / n : 0.0;
+  o[4] = row[A_NONFINITE];
+  const double x0 = static_cast<double>(pred[b * P]);
+  o[5] = x0 + row[A_SX] / Pd;
+  // unbiased.  A difference that rounds below 0 on a near-constant map is 0 (torch's two-pass value is
+  // never negative); the comparison, unlike fmax, keeps NaN, and one pixel stays 0 / 0 = NaN
+  const double dev2 = row[A_SX2] - row[A_SX] * row[A_SX] / Pd;
+  o[6] = sqrt((dev2 < 0.0 ? 0.0 : dev2) / (Pd - 1.0));
+  o[7] = row[A_MIN];
+  o[8] = row[A_MAX];
+  for (int k = 0; k < MAXT; ++k) o[9 + k] = any ? row[A_BAD + k] / n : 0.0;
+}
+
+// 4 pixels (12 bytes) per lane over the flat (B*H*W) index; the lane after the last quad takes the rest
+__global__ __launch_bounds__(256) void gt_decode_kernel(const unsigned char* __restrict__ u8, float* __restrict__ out,
+                                                        long long N, double gt_scale) {
+  const long long q = blockIdx.x * 256ll + threadIdx.x;
+  const long long nquad = N >> 2;
+  if (q > nquad) return;
+  const long long i = q << 2;
+  if (q < nquad) {
+    const uint3 w = *reinterpret_cast<const uint3*>(u8 + 3 * i);
+    float4 o;
+    o.x = decode_gt(w.x & 255u, (w.x >> 8) & 255u, (w.x >> 16) & 255u, gt_scale);
+    o.y = decode_gt(w.x >> 24, w.y & 255u, (w.y >> 8) & 255u, gt_scale);
+    o.z = decode_gt((w.y >> 16) & 255u, w.y >> 24, w.z & 255u, gt_scale);
+    o.w = decode_gt((w.z >> 8) & 255u, (w.z >> 16) & 255u, w.z >> 24, gt_scale);
+    *reinterpret_cast<float4*>(out + i) = o;
+  } else {
+    for (long long k = i; k < N; ++k) out[k] = decode_gt(u8[3 * k], u8[3 * k + 1], u8[3 * k + 2], gt_scale);
+  }
+}
+
+inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
+}  // namespace
+}  // namespace fsmi
+
+using namespace fsmi;
+
+extern "C" {
+
+int fsmi_disp_metrics_blocks(int H, int W) {
+  if (H < 1 || W < 1) return 1;
+  const long long quads = (static_cast<long long>(H) * W + 3) >> 2;
+  return static_cast<int>(std::min<long long>(std::max<long long>((quads + kQuadsPerBlock - 1) / kQuadsPerBlock, 1),
+                                              kMaxBlocks));
+}
+
+int fsmi_disp_metrics(const float* pred, const float* gt, const unsigned char* gt_u8, const unsigned char* mask,
+                      const float* thresholds, int K, double gt_scale, double* partials, double* sums, double* table,
+                      float* error, int B, int H, int W, void* stream) {
+  FSMI_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "fsmi_disp_metrics: bad shape (%d,%d,%d)", B, H, W);
+  FSMI_CHECK_ARG(K >= 0 && K <= MAXT, "fsmi_disp_metrics: K = %d thresholds: 0..%d", K, MAXT);
+  FSMI_CHECK_ARG(K == 0 || thresholds, "fsmi_disp_metrics: null thresholds with K = %d", K);
+  FSMI_CHECK_ARG((gt != nullptr) != (gt_u8 != nullptr), "fsmi_disp_metrics: exactly one of gt (fp32) and gt_u8");
+  FSMI_CHECK_ARG(!gt_u8 || gt_scale > 0.0, "fsmi_disp_metrics: gt_scale = %g must be positive", gt_scale);
+  FSMI_CHECK_ARG(pred && partials && sums && table, "fsmi_disp_metrics: null pointer");
+  const long long P = static_cast<long long>(H) * W;
+  FSMI_CHECK_ARG(P <= INT_MAX, "fsmi_disp_metrics: H*W = %lld exceeds 2^31 - 1", P);
+  FSMI_CHECK_ARG(aligned(pred, 16) && (!gt || aligned(gt, 16)) && (!gt_u8 || aligned(gt_u8, 4)) &&
+                     (!mask || aligned(mask, 4)) && (!error || aligned(error, 16)) && aligned(partials, 8) &&
+                     aligned(sums, 8) && aligned(table, 8),
+                 "fsmi_disp_metrics: fp32 maps must be 16-byte, uint8 maps 4-byte, fp64 outputs 8-byte aligned");
+  Metrics g;
+  g.P = P;
+  g.gt_scale = gt_scale;
+  for (int k = 0; k < MAXT; ++k) g.thr[k] = k < K ? thresholds[k] : INFINITY;
+  const int NB = fsmi_disp_metrics_blocks(H, W);
+  hipStream_t s = as_stream(stream);
+  if (gt_u8)
+    hipLaunchKernelGGL(disp_metrics_partial_kernel<true>, dim3(NB, B), dim3(256), 0, s, pred,
+                       static_cast<const void*>(gt_u8), mask, partials, error, g);
+  else
+    hipLaunchKernelGGL(disp_metrics_partial_kernel<false>, dim3(NB, B), dim3(256), 0, s, pred,
+                       static_cast<const void*>(gt), mask, partials, error, g);
+  hipLaunchKernelGGL(disp_metrics_finalize_kernel, dim3(B), dim3(256), 0, s, partials, pred, sums, table, NB, P);
+  return finish_launch("fsmi_disp_metrics");
+}
+
+int fsmi_gt_decode(const unsigned char* gt_u8, float* out, int B, int H, int W, double gt_scale, void* stream) {
+  FSMI_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, "fsmi_gt_decode: bad shape (%d,%d,%d)", B, H, W);
+  FSMI_CHECK_ARG(gt_scale > 0.0, "fsmi_gt_decode: gt_scale = %g must be positive", gt_scale);
+  FSMI_CHECK_ARG(gt_u8 && out, "fsmi_gt_decode: null pointer");
+  const long long N = static_cast<long long>(B) * H * W;
+  FSMI_CHECK_ARG(((N >> 2) + 256) / 256 <= INT_MAX, "fsmi_gt_decode: too many pixels");
+  FSMI_CHECK_ARG(aligned(gt_u8, 4) && aligned(out, 16), "fsmi_gt_decode: gt_u8 must be 4-byte and out 16-byte aligned");
+  hipLaunchKernelGGL(gt_decode_kernel, dim3(ceil_div((N >> 2) + 1, 256)), dim3(256), 0, as_stream(stream), gt_u8, out, N,
+                     gt_scale);
+  return finish_launch("fsmi_gt_decode");
+}
+
+}  // extern "C"

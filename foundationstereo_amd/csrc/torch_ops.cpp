@@ -14,6 +14,7 @@
 //   disp_to_xyz         scripts/run_demo.py:173-251, Utils.py:56-75
 //   radius_outlier_mask scripts/run_demo.py:270-273 (Open3D remove_radius_outlier)
 //   frames_ingest       scripts/run_demo.py:131-159   vis_disparity     Utils.py:108-133
+//   disp_metrics        train/utils.py:88-141, train/losses.py:326-339   gt_decode  Utils.py:137-140
 #include <torch/library.h>
 #include <ATen/core/Tensor.h>
 #include <ATen/ops/empty.h>
@@ -330,6 +331,63 @@ std::tuple<Tensor, Tensor> vis_disparity(const Tensor& disp_, const Tensor& lut_
   return {out, minmax};
 }
 
+// contiguous and 4-byte aligned: the metrics kernels read uint8 maps a word at a time
+Tensor dense_u8(const Tensor& t) {
+  Tensor c = t.contiguous();
+  if (reinterpret_cast<uintptr_t>(c.data_ptr()) % 4 != 0) c = c.clone();
+  return c;
+}
+
+// ops.disp_metrics: (table, sums, error); error has no element when want_error is false
+std::tuple<Tensor, Tensor, Tensor> disp_metrics(const Tensor& pred_, const Tensor& gt_, const c10::optional<Tensor>& mask_,
+                                                at::ArrayRef<double> thresholds, double gt_scale, bool want_error) {
+  const c10::DeviceGuard guard(pred_.device());
+  check_dev("disp_metrics", pred_);
+  const bool u8 = gt_.scalar_type() == at::kByte;
+  if (u8) check_u8("disp_metrics", gt_); else check_dev("disp_metrics", gt_);
+  TORCH_CHECK(pred_.dim() == 3, "disp_metrics: pred must be (B,H,W)");
+  const int64_t B = pred_.size(0), H = pred_.size(1), W = pred_.size(2);
+  TORCH_CHECK(gt_.device() == pred_.device() && gt_.dim() == (u8 ? 4 : 3) && gt_.size(0) == B && gt_.size(1) == H &&
+                  gt_.size(2) == W && (!u8 || gt_.size(3) == 3),
+              "disp_metrics: gt must be fp32 (B,H,W) or uint8 (B,H,W,3) on the device of pred");
+  TORCH_CHECK((int64_t)thresholds.size() <= FSMI_METRICS_MAX_THRESHOLDS, "disp_metrics: at most ",
+              FSMI_METRICS_MAX_THRESHOLDS, " thresholds");
+  TORCH_CHECK(!u8 || gt_scale > 0.0, "disp_metrics: gt_scale must be positive");
+  Tensor mask;
+  if (mask_.has_value() && mask_->defined()) {
+    TORCH_CHECK(mask_->is_cuda() && mask_->device() == pred_.device() &&
+                    (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
+                    mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
+                "disp_metrics: mask must be bool or uint8 (B,H,W) on the device of pred");
+    mask = dense_u8(*mask_).view(at::kByte);
+  }
+  Tensor pred = dense(pred_), gt = u8 ? dense_u8(gt_) : dense(gt_);
+  const auto f64 = pred.options().dtype(at::kDouble);
+  Tensor partials = at::empty({B, fsmi_disp_metrics_blocks((int)H, (int)W), FSMI_METRICS_NACC}, f64);
+  Tensor sums = at::empty({B, FSMI_METRICS_NACC}, f64), table = at::empty({B, FSMI_METRICS_NACC}, f64);
+  Tensor error = want_error ? at::empty({B, H, W}, pred.options()) : at::empty({0}, pred.options());
+  float thr[FSMI_METRICS_MAX_THRESHOLDS] = {};
+  for (size_t k = 0; k < thresholds.size(); ++k) thr[k] = (float)thresholds[k];
+  ok(fsmi_disp_metrics(cp(pred), u8 ? nullptr : cp(gt), u8 ? gt.data_ptr<uint8_t>() : nullptr,
+                       mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, thr, (int)thresholds.size(), gt_scale,
+                       partials.data_ptr<double>(), sums.data_ptr<double>(), table.data_ptr<double>(),
+                       want_error ? mp(error) : nullptr, B, H, W, stream_of(pred)),
+     "disp_metrics");
+  return {table, sums, error};
+}
+
+Tensor gt_decode(const Tensor& gt_u8_, double gt_scale) {
+  const c10::DeviceGuard guard(gt_u8_.device());
+  check_u8("gt_decode", gt_u8_);
+  TORCH_CHECK(gt_u8_.dim() == 4 && gt_u8_.size(3) == 3, "gt_decode: expected uint8 (B,H,W,3)");
+  TORCH_CHECK(gt_scale > 0.0, "gt_decode: gt_scale must be positive");
+  Tensor u8 = dense_u8(gt_u8_);
+  const int64_t B = u8.size(0), H = u8.size(1), W = u8.size(2);
+  Tensor out = at::empty({B, H, W}, u8.options().dtype(at::kFloat));
+  ok(fsmi_gt_decode(u8.data_ptr<uint8_t>(), mp(out), B, H, W, gt_scale, stream_of(u8)), "gt_decode");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(fsmi, m) {
@@ -353,6 +411,10 @@ TORCH_LIBRARY(fsmi, m) {
   // invalid_thres=None is +inf, the reference's default (the schema grammar has no literal for it)
   m.def("vis_disparity(Tensor disp, Tensor lut, float? min_val=None, float? max_val=None, float? invalid_thres=None, "
         "Tensor? image=None) -> (Tensor, Tensor)");
+  // scoring (train/utils.py:88-141): (table, sums, error); error is empty unless want_error
+  m.def("disp_metrics(Tensor pred, Tensor gt, Tensor? mask=None, float[] thresholds=[1.0, 3.0, 5.0], "
+        "float gt_scale=1000.0, bool want_error=False) -> (Tensor, Tensor, Tensor)");
+  m.def("gt_decode(Tensor gt_u8, float gt_scale=1000.0) -> Tensor");
 }
 
 // ROCm builds of PyTorch expose HIP devices under the CUDA dispatch key
@@ -371,4 +433,6 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("radius_outlier_mask", radius_outlier_mask);
   m.impl("frames_ingest", frames_ingest);
   m.impl("vis_disparity", vis_disparity);
+  m.impl("disp_metrics", disp_metrics);
+  m.impl("gt_decode", gt_decode);
 }

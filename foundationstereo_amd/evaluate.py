@@ -1,0 +1,106 @@
+"""Score a disparity map against a ground truth: EPE, RMSE, bad-pixel rates and D1, on the device.
+
+    # run the model on a pair, then score its disparity
+    python -m foundationstereo_amd.evaluate --left_file left.png --right_file right.png \\
+        --gt_file disp_gt.png --gt_scale 1000 --ckpt_dir pretrained_models/model_best_bp2.pth
+
+    # score two stored maps, e.g. bench.py --dump-outputs' disparity.npy of --precision fast
+    # against the default run's
+    python -m foundationstereo_amd.evaluate --pred_file fast/disparity.npy --gt_file parity/disparity.npy
+
+``--gt_file`` is a ``.npy`` float map (H,W), or the reference's 3 x uint8 encoding (Utils.py:137-140) as
+an image file or a uint8 ``.npy`` (H,W,3), decoded with ``--gt_scale``.  A pixel is scored where the
+ground truth is positive and finite; ``--all_pixels`` scores every pixel.  ``--error_png`` writes the
+error map through the disparity picture's kernels (0 .. ``--error_max`` px over the turbo table,
+unscored pixels black).  The model flags are the demo's (``demo.parser``); ``--scale`` must stay 1,
+because resizing a ground truth is not defined here.  Prints one JSON line.
+"""
+from __future__ import annotations
+
+import json
+import sys
+
+import numpy as np
+import torch
+
+from . import demo, frames, metrics
+
+
+def parser():
+    p = demo.parser()
+    p.prog = "python -m foundationstereo_amd.evaluate"
+    p.description = "Score a disparity (the model's, or a stored map) against a ground truth"
+    p.add_argument("--gt_file", required=True, type=str,
+                   help="Ground truth: .npy float map (H,W), or the 3 x uint8 encoding as an image / uint8 .npy (H,W,3)")
+    p.add_argument("--pred_file", default=None, type=str,
+                   help="Score this stored .npy disparity instead of running the model on --left_file / --right_file")
+    p.add_argument("--gt_scale", default=1000.0, type=float, help="Scale of the uint8 ground-truth encoding")
+    p.add_argument("--thresholds", default=[1.0, 3.0, 5.0], type=float, nargs="*", help="Bad-pixel thresholds in px (up to 8)")
+    p.add_argument("--all_pixels", action="store_true", help="Score every pixel (a mask of ones), not only gt > 0")
+    p.add_argument("--error_png", default=None, type=str, help="Write the error map as a PNG here")
+    p.add_argument("--error_max", default=5.0, type=float, help="Error in px at the top of the picture's colour range")
+    return p
+
+
+def read_gt(path: str, device) -> torch.Tensor:
+    """The ground truth as a device tensor: fp32 (H,W), or uint8 (H,W,3) still encoded."""
+    if path.lower().endswith(".npy"):
+        a = np.load(path)
+        if a.dtype != np.uint8:
+            a = np.squeeze(a)
+            if a.ndim != 2:
+                raise SystemExit(f"evaluate: {path}: expected a float map (H,W), got {a.shape}")
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+    else:
+        a = frames.read_image(path)
+    if a.ndim != 3 or a.shape[2] < 3:
+        raise SystemExit(f"evaluate: {path}: the uint8 encoding needs 3 channels, got {a.shape}")
+    return torch.from_numpy(np.ascontiguousarray(a[:, :, :3])).to(device)
+
+
+def predict(a, device) -> torch.Tensor:
+    """The model's unpadded disparity (H,W) of the pair: demo.run_pair's own ingest, forward and unpad,
+    without the cloud (it reads no intrinsics then; its picture, two launches, is not used)."""
+    model = demo.load_model(a, device)
+    left, right = frames.read_image(a.left_file), frames.read_image(a.right_file)
+    return demo.run_pair(model, left, right, None, None, hiera=a.hiera, valid_iters=a.valid_iters, get_pc=0)["disp"]
+
+
+def main(argv=None) -> dict:
+    a = parser().parse_args(argv)
+    if a.scale != 1:
+        raise SystemExit("evaluate: --scale must be 1: resizing a ground truth is not defined here")
+    if len(a.thresholds) > metrics.MAX_THRESHOLDS:
+        raise SystemExit(f"evaluate: at most {metrics.MAX_THRESHOLDS} thresholds")
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluate: needs a HIP device")
+    device = torch.device("cuda", torch.cuda.current_device())
+    if a.pred_file is not None:
+        pred = np.squeeze(np.load(a.pred_file))
+        if pred.ndim != 2:
+            raise SystemExit(f"evaluate: {a.pred_file}: expected a disparity map (H,W), got {pred.shape}")
+        pred = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).to(device)
+    else:
+        pred = predict(a, device)
+    gt = read_gt(a.gt_file, device)
+    if tuple(gt.shape[:2]) != tuple(pred.shape):
+        raise SystemExit(f"evaluate: ground truth {tuple(gt.shape[:2])} against a disparity of {tuple(pred.shape)}")
+    mask = torch.ones(pred.shape, dtype=torch.bool, device=device) if a.all_pixels else None
+    m = metrics.stereo_metrics(pred, gt, mask, a.thresholds, a.gt_scale, want_error=a.error_png is not None)
+    if a.error_png is not None:
+        frames.write_png(a.error_png, frames.vis_disparity(m.error, min_val=0.0, max_val=a.error_max)[0])
+    row = m.table[0].cpu().tolist()                         # the one read-back
+    res = {"mode": "pred_file" if a.pred_file is not None else "model", "image_size": list(pred.shape),
+           "n_valid": int(row[metrics.N_VALID]), "n_nonfinite": int(row[metrics.N_NONFINITE]),
+           "epe": row[metrics.EPE], "rmse": row[metrics.RMSE], "d1_all": row[metrics.D1_ALL],
+           "thresholds": list(m.thresholds), "bad": row[metrics.BAD0:metrics.BAD0 + len(m.thresholds)],
+           "pred_mean": row[metrics.PRED_MEAN], "pred_std": row[metrics.PRED_STD],
+           "pred_min": row[metrics.PRED_MIN], "pred_max": row[metrics.PRED_MAX]}
+    if a.error_png is not None:
+        res["error_png"] = a.error_png
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from typing import List, Sequence
 
+import ctypes
 import json
 import os
 
@@ -1324,4 +1325,81 @@ def disp_colorize(disp: Tensor, minmax: Tensor, lut: Tensor, invalid_thres: floa
     out = torch.empty((B, H, 2 * W if image is not None else W, 3), device=disp.device, dtype=torch.uint8)
     _lib.check(_lib.load().fsmi_disp_colorize(_p(disp), _p(minmax), _p(lut), _p(image) if image is not None else None,
                                               _p(out), B, H, W, float(invalid_thres), _stream(disp)), "disp_colorize")
+    return out
+
+
+# ---------------------------------------------------------------- scoring against a ground truth
+
+METRICS_NACC = 17           # FSMI_METRICS_NACC
+METRICS_MAX_THRESHOLDS = 8  # FSMI_METRICS_MAX_THRESHOLDS
+
+
+def disp_metrics_blocks(H: int, W: int) -> int:
+    """Blocks per pair of the metrics pass (a function of H * W only); sizes the workspace."""
+    return int(_lib.load().fsmi_disp_metrics_blocks(int(H), int(W)))
+
+
+def _u8_aligned(t: Tensor) -> Tensor:
+    """Contiguous and 4-byte aligned (the kernels read uint8 maps a word at a time)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 4 == 0 else t.clone()
+
+
+def disp_metrics(pred: Tensor, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.0), gt_scale: float = 1000.0,
+                 want_error: bool = False):
+    """train/utils.py:88-141 + train/losses.py:326-339 per pair, in two launches and without a host
+    synchronisation.  pred fp32 (B,H,W); gt fp32 (B,H,W), or uint8 (B,H,W,3) in the reference's
+    encoding (decoded with ``gt_scale``); mask None (valid where gt > 0 and finite) or bool / uint8
+    (B,H,W); up to 8 thresholds -> (table (B,17) fp64, sums (B,17) fp64, error (B,H,W) fp32 or None).
+    include/fsmi.h has the layout of the two rows and the arithmetic."""
+    _check("disp_metrics", pred)
+    if not isinstance(gt, torch.Tensor):
+        raise TypeError("disp_metrics: expected tensors")
+    u8 = gt.dtype == torch.uint8
+    (_check_u8 if u8 else _check)("disp_metrics", gt)
+    if pred.dim() != 3:
+        raise RuntimeError(f"disp_metrics: pred must be (B,H,W), got {tuple(pred.shape)}")
+    B, H, W = pred.shape
+    if tuple(gt.shape) != ((B, H, W, 3) if u8 else (B, H, W)) or gt.device != pred.device:
+        raise RuntimeError(f"disp_metrics: gt must be fp32 ({B},{H},{W}) or uint8 ({B},{H},{W},3) on the device of "
+                           f"pred, got {gt.dtype} {tuple(gt.shape)}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("disp_metrics: mask must be a bool or uint8 tensor")
+        _check_u8("disp_metrics", mask.view(torch.uint8))
+        if tuple(mask.shape) != (B, H, W) or mask.device != pred.device:
+            raise RuntimeError(f"disp_metrics: mask must be ({B},{H},{W}) on the device of pred, got {tuple(mask.shape)}")
+        mask = _u8_aligned(mask).view(torch.uint8)
+    thr = [float(t) for t in thresholds]
+    if len(thr) > METRICS_MAX_THRESHOLDS:
+        raise RuntimeError(f"disp_metrics: {len(thr)} thresholds, at most {METRICS_MAX_THRESHOLDS}")
+    if u8 and not float(gt_scale) > 0.0:
+        raise RuntimeError(f"disp_metrics: gt_scale = {gt_scale} must be positive")
+    lib = _lib.load()
+    pred, gt = _c(pred), (_u8_aligned(gt) if u8 else _c(gt))
+    dev = pred.device
+    partials = torch.empty((B, disp_metrics_blocks(H, W), METRICS_NACC), device=dev, dtype=torch.float64)
+    sums = torch.empty((B, METRICS_NACC), device=dev, dtype=torch.float64)
+    table = torch.empty((B, METRICS_NACC), device=dev, dtype=torch.float64)
+    error = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_error else None
+    cthr = (ctypes.c_float * max(len(thr), 1))(*thr)        # rounded to fp32 here, compared in fp32
+    _lib.check(lib.fsmi_disp_metrics(_p(pred), None if u8 else _p(gt), _p(gt) if u8 else None,
+                                     _p(mask) if mask is not None else None, cthr, len(thr), float(gt_scale),
+                                     _p(partials), _p(sums), _p(table), _p(error) if want_error else None, B, H, W,
+                                     _stream(pred)), "disp_metrics")
+    return table, sums, error
+
+
+def gt_decode(gt_u8: Tensor, gt_scale: float = 1000.0) -> Tensor:
+    """Utils.py:137-140 on the device: uint8 (B,H,W,3) -> fp32 (B,H,W), float32 of the reference's
+    float64 ``(r * 255 * 255 + g * 255 + b) / scale``."""
+    _check_u8("gt_decode", gt_u8)
+    if gt_u8.dim() != 4 or gt_u8.shape[3] != 3:
+        raise RuntimeError(f"gt_decode: expected uint8 (B,H,W,3), got {tuple(gt_u8.shape)}")
+    if not float(gt_scale) > 0.0:
+        raise RuntimeError(f"gt_decode: gt_scale = {gt_scale} must be positive")
+    B, H, W, _ = gt_u8.shape
+    gt_u8 = _u8_aligned(gt_u8)
+    out = torch.empty((B, H, W), device=gt_u8.device, dtype=torch.float32)
+    _lib.check(_lib.load().fsmi_gt_decode(_p(gt_u8), _p(out), B, H, W, float(gt_scale), _stream(gt_u8)), "gt_decode")
     return out

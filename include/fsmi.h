@@ -457,6 +457,52 @@ int fsmi_disp_minmax(const float* disp, float* minmax, int B, int H, int W, floa
 int fsmi_disp_colorize(const float* disp, const float* minmax, const unsigned char* lut, const unsigned char* image,
                        unsigned char* out, int B, int H, int W, float invalid_thres, void* stream);
 
+/* ---- scoring a disparity map against a ground truth ----------------------
+ * Per-pair EPE, RMSE, bad-pixel rates, KITTI's D1 and the prediction's own statistics; replaces
+ * compute_stereo_metrics (train/utils.py:88-141, train/losses.py:342-376) and monitoring_stereo
+ * (train/losses.py:326-339), which gather through a boolean mask and read 4 + K scalars back per pair.
+ * Nothing below synchronises the host or allocates; all of it can be captured in a hipGraph.  Sums
+ * are fp64 and no float atomic is used: every addition's order is fixed by (H*W, the block count)
+ * alone, and the block count by H*W alone, so equal inputs give equal bits on every device.
+ *
+ * pred: fp32 (B,H,W), 16-byte aligned.  The ground truth is exactly one of
+ *   gt      fp32 (B,H,W), 16-byte aligned, or
+ *   gt_u8   uint8 (B,H,W,3), 4-byte aligned, the reference's encoding (depth_uint8_decoding,
+ *           Utils.py:137-140):  n = r * 65025 + g * 255 + b  (int32, at most 16 605 816),
+ *           gt = (float)((double)n / gt_scale), gt_scale > 0
+ * mask: NULL, or uint8 (B,H,W), 4-byte aligned.  A pixel is VALID where mask != 0 when a mask is
+ * given (the mask alone decides, as in the reference); otherwise where gt > 0 && gt < +inf (the
+ * dataloader's rule, train/dataloader.py:142-148, with NaN and inf ground truth invalid).
+ * thresholds: K <= FSMI_METRICS_MAX_THRESHOLDS fp32 values in HOST memory, read before the call returns.
+ * Per valid pixel, in un-contracted fp32 as torch evaluates it on fp32 tensors:
+ *   e = fabsf(pred - gt);   bad[k] counts e > thresholds[k];   d1 counts e > 3 && e > 0.05f * fabsf(gt)
+ *   (KITTI's D1-all); e and e * e are widened to fp64 before they are added.
+ * NaN and inf propagate as in torch: a NaN prediction under a valid pixel makes the sums NaN, is "not
+ * bad" in every rate (NaN > t is false) and is counted in n_nonfinite.
+ * partials: workspace, (B, fsmi_disp_metrics_blocks of (H,W), FSMI_METRICS_NACC) fp64; every row is
+ * written, none is read before it is.  sums, table: (B, FSMI_METRICS_NACC) fp64.
+ *   sums[b]  = [n_valid, sum e, sum e^2, n_d1, n_nonfinite, sum (x - x0), sum (x - x0)^2, min x, max x,
+ *               n_bad[0..7]]   x = pred over ALL pixels of the pair, x0 = pred[b,0,0] (the shift keeps
+ *               the one-pass variance well conditioned); counts are exact doubles; min and max
+ *               propagate NaN; unused n_bad slots are 0.  The sums of several calls add.
+ *   table[b] = [n_valid, epe, rmse, d1_all, n_nonfinite, pred_mean, pred_std, pred_min, pred_max,
+ *               bad[0..7]]   epe = sum e / n, rmse = sqrt(sum e^2 / n), rates = count / n, all fp64;
+ *               n_valid == 0 gives epe = rmse = d1_all = bad[k] = 0 (train/utils.py:122-123);
+ *               pred_std is the unbiased one (torch's default), NaN for a one-pixel map; a sum of
+ *               squared deviations that rounds below 0 counts as 0.
+ * error: NULL, or fp32 (B,H,W), 16-byte aligned: e on valid pixels, +inf on invalid ones (with
+ * fsmi_disp_colorize at min 0, max tau: an error picture whose invalid pixels are black). */
+#define FSMI_METRICS_NACC 17
+#define FSMI_METRICS_MAX_THRESHOLDS 8
+/* Blocks per pair of the streaming pass: a function of H * W only, never of the device; >= 1. */
+int fsmi_disp_metrics_blocks(int H, int W);
+int fsmi_disp_metrics(const float* pred, const float* gt, const unsigned char* gt_u8, const unsigned char* mask,
+                      const float* thresholds, int K, double gt_scale, double* partials, double* sums, double* table,
+                      float* error, int B, int H, int W, void* stream);
+/* The ground-truth map itself: gt_u8 uint8 (B,H,W,3), 4-byte aligned -> out fp32 (B,H,W), 16-byte
+ * aligned, the arithmetic above (bit-equal to float32 of the reference's float64 decode). */
+int fsmi_gt_decode(const unsigned char* gt_u8, float* out, int B, int H, int W, double gt_scale, void* stream);
+
 /* ---- live kernel timing (bench.py roofline) -----------------------------
  * When enabled, every launch of the kernels below is bracketed by a pair of
  * hipEvents recorded on the launch stream (skipped while the stream is being

@@ -301,14 +301,61 @@ def frames():
     print("frames_small", {k: (v.shape, v.dtype) for k, v in g.items()})
 
 
+def _load_by_path(name, *parts):
+    import importlib.util
+    from ref_harness import REF_ROOT
+    spec = importlib.util.spec_from_file_location(name, os.path.join(REF_ROOT, *parts))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def metrics():
+    """compute_stereo_metrics (train/utils.py:88-141), monitoring_stereo (train/losses.py:326-339) and
+    depth_uint8_decoding (Utils.py:137-140) run by the reference on a (3,37,61) case whose ground truth
+    is the decoded uint8 map: pins tests/metrics_oracle.py.  Pair 1's mask is empty (:122-123).  The
+    inputs come from tests/metrics_oracle.py golden_case (hash PRNG); the file holds the reference's
+    outputs, 8 decoded rows and checksums of the inputs."""
+    import_reference()
+    import importlib
+    ref_utils = importlib.import_module("Utils")
+    train_utils = _load_by_path("ref_train_utils", "train", "utils.py")
+    train_losses = _load_by_path("ref_train_losses", "train", "losses.py")
+    from tests import metrics_oracle
+    case = metrics_oracle.golden_case()                     # the tests regenerate the same inputs
+    gt_u8, gt, pred, mask, thresholds = (case[k] for k in ("gt_u8", "gt", "pred", "mask", "thresholds"))
+    B = len(pred)
+    gt64 = np.stack([ref_utils.depth_uint8_decoding(gt_u8[b], scale=1000) for b in range(B)])
+    assert np.array_equal(gt, gt64.astype(np.float32))      # the inputs were built on the oracle's decode
+    # the reference's float64 decode of 8 rows of pair 0 (the arithmetic is per pixel)
+    g = {"gt0_decoded_f64": gt64[0, :8], "thresholds": np.array(thresholds),
+         "checksums": np.array([float(gt_u8.sum()), float(pred.astype(np.float64).sum()), float(mask.sum())])}
+    whole = train_utils.compute_stereo_metrics(t(pred), t(gt), t(mask), thresholds)
+    keys = sorted(whole)
+    g["keys"] = np.array(keys)
+    g["batch"] = np.array([whole[k] for k in keys], dtype=np.float64)
+    for b in range(B):
+        one = train_utils.compute_stereo_metrics(t(pred[b]), t(gt[b]), t(mask[b]), thresholds)
+        two = train_losses.compute_stereo_metrics(t(pred[b]), t(gt[b]), t(mask[b]), thresholds)
+        assert all(one[k] == two[k] for k in two)
+        g[f"pair{b}"] = np.array([one[k] for k in keys], dtype=np.float64)
+        mon = train_losses.monitoring_stereo(t(pred[b]))
+        g[f"monitoring{b}"] = np.array([mon[k] for k in ("disparity_mean", "disparity_std", "disparity_min",
+                                                         "disparity_max")], dtype=np.float64)
+    np.savez_compressed(os.path.join(OUT, "metrics_small.npz"), **g)
+    print("metrics_small", {k: (v.shape, v.dtype) for k, v in g.items()}, keys)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud", "frames"]
+    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud", "frames", "metrics"]
     if "cloud" in which:
         cloud()
     if "frames" in which:
         frames()
-    if set(which) <= {"cloud", "frames"}:
+    if "metrics" in which:
+        metrics()
+    if set(which) <= {"cloud", "frames", "metrics"}:
         return
     fs, sm, geo_mod, up_mod, ut = import_reference()
     if "backbone" in which:
