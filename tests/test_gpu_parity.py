@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 import oracle
 from foundationstereo_amd import synth
+from tests.conv_tiles import HALO_2D
 from tests.helpers import load_golden, model_keys, oracle_params, t
 
 pytestmark = pytest.mark.gpu
@@ -166,14 +167,16 @@ def test_conv3d_direct_vs_torch(ops_mod, KS, shape):
 
 @pytest.mark.parametrize("HW", [(19, 45), (12, 40)])
 @pytest.mark.parametrize("nsplit", [1, 2])
-@pytest.mark.parametrize("cfg", [-1, 0, 1, 2, 3, 4, 5, 8, 9, 11, 19, 20, 21, 23])
-@pytest.mark.parametrize("k,cout,act", [(3, 37, "relu"), (1, 70, "gelu"), (3, 136, None), (1, 129, "relu")])
+@pytest.mark.parametrize("cfg", [c for c in HALO_2D if c < 32])
+@pytest.mark.parametrize("k,cout,act", [(3, 37, "relu"), (1, 70, "gelu"), (3, 136, None), (1, 129, "relu"),
+                                        (3, 24, "relu"), (1, 24, None)])
 def test_conv2d_halo_vs_torch(ops_mod, cfg, k, cout, act, nsplit, HW):
-    """Halo-tiled split-precision conv (cfg 0/1 weights via LDS, 2-5, 8, 9 in registers, 16+c the
+    """Halo-tiled split-precision conv (cfg 0/1 weights via LDS, 2-9, 11 in registers, 16+c the
     K-group variants: two wave groups per block on alternate chunks): 2 segments (16 channels + a 29-channel slice -> 2 channel
     chunks, ragged last chunk), ragged row/column tiles (19x45; 12x40 takes the float4 split-K
-    reduce), ragged couts, output slice, every epilogue term, with and without split-K; vs fp64
-    torch.  Same 2e-5 abs + 1e-5 rel tolerance as the im2col kernels."""
+    reduce), ragged couts (24: the policy's 32-cout tile 6 through cfg -1), output slice, every epilogue
+    term, with and without split-K; vs fp64 torch.  Same 2e-5 abs + 1e-5 rel tolerance as the im2col
+    kernels."""
     import torch.nn.functional as F
     B, (H, W) = 2, HW
     a_ = synth.normal(191, (B, 16, H, W))
