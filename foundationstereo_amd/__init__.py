@@ -8,7 +8,9 @@ depth, XYZ map and denoised point cloud from the disparity, ``frames``: camera
 frames to model input and the disparity picture, ``demo``: the reference's
 demo end to end (``python -m foundationstereo_amd.demo``), and ``metrics``:
 EPE / RMSE / bad-pixel rates / D1 of a disparity against a ground truth
-(``python -m foundationstereo_amd.evaluate``).  See DESIGN.md.
+(``python -m foundationstereo_amd.evaluate``), and ``losses``: every
+refinement iteration scored in one pass, the reference's sequence loss and
+the convergence curve (``evaluate --per_iter``).  See DESIGN.md.
 """
 import os as _os
 
@@ -28,6 +30,7 @@ if _os.path.isdir(_TUNING):
 
 _METRICS = ("stereo_metrics", "compute_stereo_metrics", "monitoring_stereo", "decode_gt", "MetricsAccumulator",
             "StereoMetrics")
+_LOSSES = ("sequence_metrics", "foundation_stereo_loss", "SequenceMetrics", "SequenceAccumulator")
 
 
 def __getattr__(name):
@@ -35,6 +38,9 @@ def __getattr__(name):
     if name in _METRICS:
         from . import metrics
         return getattr(metrics, name)
+    if name in _LOSSES:
+        from . import losses
+        return getattr(losses, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -78,6 +78,11 @@ SIGNATURES = {
     "fsmi_disp_metrics_blocks": [_I, _I],
     "fsmi_disp_metrics": [_P, _P, _P, _P, ctypes.POINTER(_F), _I, ctypes.c_double, _P, _P, _P, _P, _I, _I, _I, _P],
     "fsmi_gt_decode": [_P, _P, _I, _I, _I, ctypes.c_double, _P],
+    "fsmi_seq_metrics_blocks": [_I, _I, _I],
+    "fsmi_seq_metrics": [_PP, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(_I),
+                         ctypes.POINTER(_I), ctypes.POINTER(_F), ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_double),
+                         ctypes.c_char_p, _I, _P, _P, _P, ctypes.POINTER(_F), _I, ctypes.c_double, _F, _P, _P, _P, _P,
+                         _I, _I, _I, _P],
     "fsmi_debug_conv_timestamps": [_P],
     "fsmi_range_status": [_I, ctypes.POINTER(_I)],
     "fsmi_set_range_safe": [_I],

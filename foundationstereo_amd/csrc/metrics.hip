@@ -14,7 +14,7 @@
 #include <climits>
 #include <cstdint>
 
-#include "fsmi_common.h"
+#include "metrics_common.h"
 
 namespace fsmi {
 namespace {
@@ -64,11 +64,6 @@ __device__ __forceinline__ double block_reduce(double (&v)[NACC], double (*lds)[
   return r;
 }
 
-__device__ __forceinline__ float decode_gt(unsigned r, unsigned g, unsigned b, double gt_scale) {
-  const int n = static_cast<int>(r * 65025u + g * 255u + b);          // <= 16 605 816
-  return static_cast<float>(static_cast<double>(n) / gt_scale);
-}
-
 // One lane's running row.  Counts stay below 2^32 per lane (a pair has at most 2^31 - 1 pixels).
 struct Lane {
   double se = 0.0, se2 = 0.0, sx = 0.0, sx2 = 0.0;
@@ -85,7 +80,7 @@ __device__ __forceinline__ float take(Lane& a, float x, float gt, bool has_mask,
   a.sx2 += dx * dx;
   a.mn = (x < a.mn || x != x) ? x : a.mn;
   a.mx = (x > a.mx || x != x) ? x : a.mx;
-  const bool valid = has_mask ? m != 0 : (gt > 0.f && gt < INFINITY);
+  const bool valid = pixel_valid(has_mask, m, gt);
   if (!valid) return INFINITY;
   const float e = fabsf(x - gt);
   const double ed = static_cast<double>(e);

@@ -15,6 +15,7 @@
 //   radius_outlier_mask scripts/run_demo.py:270-273 (Open3D remove_radius_outlier)
 //   frames_ingest       scripts/run_demo.py:131-159   vis_disparity     Utils.py:108-133
 //   disp_metrics        train/utils.py:88-141, train/losses.py:326-339   gt_decode  Utils.py:137-140
+//   seq_metrics         train/losses.py:20-187, :379-498
 #include <torch/library.h>
 #include <ATen/core/Tensor.h>
 #include <ATen/ops/empty.h>
@@ -388,6 +389,75 @@ Tensor gt_decode(const Tensor& gt_u8_, double gt_scale) {
   return out;
 }
 
+// ops.seq_metrics: (table, sums, loss) of a sequence of maps; the rows keep their strides
+std::tuple<Tensor, Tensor, Tensor> seq_metrics(at::TensorList preds_, const Tensor& gt_, const c10::optional<Tensor>& mask_,
+                                               at::ArrayRef<double> thresholds, c10::optional<double> max_disparity,
+                                               double beta, c10::optional<at::ArrayRef<double>> weights_,
+                                               at::IntArrayRef smooth_rows, double gt_scale) {
+  const c10::DeviceGuard guard(gt_.device());
+  const int64_t R = (int64_t)preds_.size();
+  TORCH_CHECK(R >= 1 && R <= FSMI_SEQ_MAX_ROWS, "seq_metrics: ", R, " rows, 1..", FSMI_SEQ_MAX_ROWS);
+  const bool u8 = gt_.scalar_type() == at::kByte;
+  if (u8) check_u8("seq_metrics", gt_); else check_dev("seq_metrics", gt_);
+  TORCH_CHECK(gt_.dim() == (u8 ? 4 : 3) && (!u8 || gt_.size(3) == 3),
+              "seq_metrics: gt must be fp32 (B,H,W) or uint8 (B,H,W,3)");
+  const int64_t B = gt_.size(0), H = gt_.size(1), W = gt_.size(2);
+  TORCH_CHECK((int64_t)thresholds.size() <= FSMI_METRICS_MAX_THRESHOLDS, "seq_metrics: at most ",
+              FSMI_METRICS_MAX_THRESHOLDS, " thresholds");
+  TORCH_CHECK(!u8 || gt_scale > 0.0, "seq_metrics: gt_scale must be positive");
+  TORCH_CHECK(beta >= 0.0, "seq_metrics: beta must not be negative");
+  TORCH_CHECK(!weights_.has_value() || (int64_t)weights_->size() == R, "seq_metrics: one weight per row");
+  const float maxd = max_disparity.has_value() ? (float)*max_disparity : INFINITY;
+  TORCH_CHECK(!(maxd != maxd), "seq_metrics: max_disparity is NaN");
+  std::vector<Tensor> keep;
+  std::vector<const float*> rows;
+  std::vector<long long> bs, rs;
+  std::vector<int> hs, ws;
+  std::vector<float> muls(R, 1.0f), maxds(R, maxd);
+  std::vector<double> weights(R, 1.0);
+  std::vector<unsigned char> smooth(R, 0);
+  for (int64_t r = 0; r < R; ++r) {
+    const Tensor& p = preds_[r];
+    check_dev("seq_metrics", p);
+    TORCH_CHECK(p.dim() == 3 && p.size(0) == B && p.size(1) >= 1 && p.size(2) >= 1 && p.device() == gt_.device(),
+                "seq_metrics: row ", r, " must be (B,h,w) on the device of gt");
+    keep.push_back(p.stride(2) == 1 && p.stride(1) >= p.size(2) && p.stride(0) >= 0 ? p : p.contiguous());
+    const Tensor& q = keep.back();
+    rows.push_back(cp(q));
+    bs.push_back(q.stride(0));
+    rs.push_back(q.stride(1));
+    hs.push_back((int)q.size(1));
+    ws.push_back((int)q.size(2));
+    if (weights_.has_value()) weights[r] = (*weights_)[r];
+  }
+  for (int64_t r : smooth_rows) {
+    TORCH_CHECK(r >= 0 && r < R, "seq_metrics: smooth row ", r, " of ", R, " rows");
+    smooth[r] = 1;
+  }
+  Tensor mask;
+  if (mask_.has_value() && mask_->defined()) {
+    TORCH_CHECK(mask_->is_cuda() && mask_->device() == gt_.device() &&
+                    (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
+                    mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
+                "seq_metrics: mask must be bool or uint8 (B,H,W) on the device of gt");
+    mask = mask_->contiguous().view(at::kByte);
+  }
+  Tensor gt = gt_.contiguous();
+  const auto f64 = gt.options().dtype(at::kDouble);
+  Tensor partials = at::empty({B, R, fsmi_seq_metrics_blocks((int)H, (int)W, (int)R), FSMI_SEQ_NACC}, f64);
+  Tensor sums = at::empty({B, R, FSMI_SEQ_NACC}, f64), table = at::empty({B, R, FSMI_SEQ_NACC}, f64);
+  Tensor loss = at::empty({B}, f64);
+  float thr[FSMI_METRICS_MAX_THRESHOLDS] = {};
+  for (size_t k = 0; k < thresholds.size(); ++k) thr[k] = (float)thresholds[k];
+  ok(fsmi_seq_metrics(rows.data(), bs.data(), rs.data(), hs.data(), ws.data(), muls.data(), maxds.data(), weights.data(),
+                      smooth.data(), (int)R, u8 ? nullptr : cp(gt), u8 ? gt.data_ptr<uint8_t>() : nullptr,
+                      mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, thr, (int)thresholds.size(), gt_scale,
+                      (float)beta, partials.data_ptr<double>(), sums.data_ptr<double>(), table.data_ptr<double>(),
+                      loss.data_ptr<double>(), B, H, W, stream_of(gt)),
+     "seq_metrics");
+  return {table, sums, loss};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(fsmi, m) {
@@ -415,6 +485,10 @@ TORCH_LIBRARY(fsmi, m) {
   m.def("disp_metrics(Tensor pred, Tensor gt, Tensor? mask=None, float[] thresholds=[1.0, 3.0, 5.0], "
         "float gt_scale=1000.0, bool want_error=False) -> (Tensor, Tensor, Tensor)");
   m.def("gt_decode(Tensor gt_u8, float gt_scale=1000.0) -> Tensor");
+  // a whole sequence of maps (train/losses.py:379-498): (table, sums, loss); max_disparity=None is +inf, no clamp
+  m.def("seq_metrics(Tensor[] preds, Tensor gt, Tensor? mask=None, float[] thresholds=[1.0, 3.0, 5.0], "
+        "float? max_disparity=None, float beta=1.0, float[]? weights=None, int[] smooth_rows=[], "
+        "float gt_scale=1000.0) -> (Tensor, Tensor, Tensor)");
 }
 
 // ROCm builds of PyTorch expose HIP devices under the CUDA dispatch key
@@ -435,4 +509,5 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("vis_disparity", vis_disparity);
   m.impl("disp_metrics", disp_metrics);
   m.impl("gt_decode", gt_decode);
+  m.impl("seq_metrics", seq_metrics);
 }

@@ -12,7 +12,13 @@
 an image file or a uint8 ``.npy`` (H,W,3), decoded with ``--gt_scale``.  A pixel is scored where the
 ground truth is positive and finite; ``--all_pixels`` scores every pixel.  ``--error_png`` writes the
 error map through the disparity picture's kernels (0 .. ``--error_max`` px over the turbo table,
-unscored pixels black).  The model flags are the demo's (``demo.parser``); ``--scale`` must stay 1,
+unscored pixels black).  ``--per_iter`` scores every refinement iteration in one pass (``losses``): the model
+runs ``forward(test_mode=False)``, each iteration's disparity is unpadded as a view, and the JSON line
+gains a ``per_iter`` object with the convergence curve (``epe``, ``rmse``, ``d1_all``, ``bad`` per
+iteration), the initial disparity's row (``init``: resized to full size and multiplied by 4), the
+sequence ``loss`` and ``first_iter_within``, the first iteration whose EPE is within ``--converged_px`` of
+the last one's; the other fields stay those of the last iteration.  With ``--per_iter``, ``--pred_file``
+names a stored sequence (K,H,W).  The model flags are the demo's (``demo.parser``); ``--scale`` must stay 1,
 because resizing a ground truth is not defined here.  Prints one JSON line.
 """
 from __future__ import annotations
@@ -23,7 +29,7 @@ import sys
 import numpy as np
 import torch
 
-from . import demo, frames, metrics
+from . import demo, frames, losses, metrics
 
 
 def parser():
@@ -39,6 +45,12 @@ def parser():
     p.add_argument("--all_pixels", action="store_true", help="Score every pixel (a mask of ones), not only gt > 0")
     p.add_argument("--error_png", default=None, type=str, help="Write the error map as a PNG here")
     p.add_argument("--error_max", default=5.0, type=float, help="Error in px at the top of the picture's colour range")
+    p.add_argument("--per_iter", action="store_true",
+                   help="Score every refinement iteration (forward(test_mode=False)); --pred_file then names a (K,H,W) .npy")
+    p.add_argument("--converged_px", default=0.01, type=float,
+                   help="With --per_iter: first_iter_within reports the first iteration whose EPE is this close to the last one's")
+    p.add_argument("--gamma", default=0.9, type=float, help="With --per_iter: the sequence loss's weight factor")
+    p.add_argument("--max_disparity", default=192.0, type=float, help="With --per_iter: the sequence loss clamps to [0, this]")
     return p
 
 
@@ -66,6 +78,81 @@ def predict(a, device) -> torch.Tensor:
     return demo.run_pair(model, left, right, None, None, hiera=a.hiera, valid_iters=a.valid_iters, get_pc=0)["disp"]
 
 
+def predict_sequence(a, device):
+    """The model's (initial disparity or None, [every iteration's unpadded disparity (1,H,W)]) of the pair:
+    ``forward(test_mode=False)`` under no_grad, each map unpadded as a view.  The quarter-resolution
+    initial disparity covers the PADDED frame: it goes out as it is when the frame needed no padding
+    (the scoring pass resizes it), else resized to the padded size first and unpadded like the rest."""
+    import torch.nn.functional as F
+    model = demo.load_model(a, device)
+    fr = frames.ingest(frames.read_image(a.left_file), frames.read_image(a.right_file), scale=a.scale)
+    if len(fr.batch) != 1:
+        raise SystemExit(f"evaluate: one pair at a time, got a batch of {len(fr.batch)}")
+    with torch.no_grad():
+        init, preds = model.forward(fr.left, fr.right, iters=a.valid_iters, test_mode=False)
+    init = init.float()
+    if any(fr.padder._pad):
+        init = fr.padder.unpad(F.interpolate(init[:, None] if init.dim() == 3 else init, size=fr.left.shape[-2:],
+                                             mode="bilinear", align_corners=False))
+    return (init[:, 0] if init.dim() == 4 else init), [fr.padder.unpad(p.float())[:, 0] for p in preds]
+
+
+def per_iter(a, device) -> dict:
+    """--per_iter: the whole sequence scored in one call, one read-back."""
+    if a.hiera:
+        raise SystemExit("evaluate: --per_iter refuses --hiera 1: run_hierachical(test_mode=False) unpads a tuple, "
+                         "in the reference as here, so its sequence is undefined")
+    if a.error_png is not None:
+        raise SystemExit("evaluate: --per_iter writes no error map: score the last iteration without it")
+    if a.pred_file is not None:
+        seq = np.load(a.pred_file)
+        if seq.ndim != 3:
+            raise SystemExit(f"evaluate: --per_iter --pred_file {a.pred_file}: expected a stored sequence (K,H,W), "
+                             f"got {seq.shape}")
+        seq = torch.from_numpy(np.ascontiguousarray(seq, dtype=np.float32)).to(device)
+        init, preds = None, [seq[k][None] for k in range(len(seq))]
+    else:
+        init, preds = predict_sequence(a, device)
+    if not 1 <= len(preds) <= losses.MAX_ROWS - 1:
+        raise SystemExit(f"evaluate: --per_iter scores 1..{losses.MAX_ROWS - 1} iterations, got {len(preds)}")
+    gt = read_gt(a.gt_file, device)
+    H, W = preds[-1].shape[-2:]
+    if tuple(gt.shape[:2]) != (H, W):
+        raise SystemExit(f"evaluate: ground truth {tuple(gt.shape[:2])} against a disparity of {(H, W)}")
+    mask = torch.ones((1, H, W), dtype=torch.bool, device=device) if a.all_pixels else None
+    m = losses.sequence_metrics(init, preds, gt[None], mask, a.gamma, a.max_disparity, a.thresholds, init_scale=4.0,
+                                gt_scale=a.gt_scale)
+    # the fields of the plain call, from the unclamped last iteration: the merged single-map stage on its view
+    last = metrics.stereo_metrics(preds[-1], gt, None if mask is None else mask[0], a.thresholds, a.gt_scale)
+    flat = torch.cat([m.table[0].reshape(-1), m.loss, last.table[0]]).cpu().tolist()       # the one read-back
+    R, n = len(preds) + int(init is not None), losses.NACC
+    rows = [flat[r * n:(r + 1) * n] for r in range(R)]
+    loss, row = flat[R * n], flat[R * n + 1:]
+    K = len(m.thresholds)
+
+    def pick(r):
+        return {"n_valid": int(r[losses.N_VALID]), "n_nonfinite": int(r[losses.N_NONFINITE]), "epe": r[losses.EPE],
+                "rmse": r[losses.RMSE], "d1_all": r[losses.D1_ALL], "bad": r[losses.BAD0:losses.BAD0 + K]}
+
+    its = rows[1:] if init is not None else rows
+    epe = [r[losses.EPE] for r in its]
+    within = [k + 1 for k, e in enumerate(epe) if abs(e - epe[-1]) <= a.converged_px]
+    res = {"mode": "pred_file" if a.pred_file is not None else "model", "image_size": [H, W],
+           "n_valid": int(row[metrics.N_VALID]), "n_nonfinite": int(row[metrics.N_NONFINITE]),
+           "epe": row[metrics.EPE], "rmse": row[metrics.RMSE], "d1_all": row[metrics.D1_ALL],
+           "thresholds": list(m.thresholds), "bad": row[metrics.BAD0:metrics.BAD0 + K],
+           "pred_mean": row[metrics.PRED_MEAN], "pred_std": row[metrics.PRED_STD],
+           "pred_min": row[metrics.PRED_MIN], "pred_max": row[metrics.PRED_MAX],
+           "per_iter": {"iters": len(its), "epe": epe, "rmse": [r[losses.RMSE] for r in its],
+                        "d1_all": [r[losses.D1_ALL] for r in its],
+                        "bad": [r[losses.BAD0:losses.BAD0 + K] for r in its],
+                        "init": pick(rows[0]) if init is not None else None, "loss": loss, "gamma": a.gamma,
+                        "max_disparity": a.max_disparity, "converged_px": a.converged_px,
+                        "first_iter_within": within[0] if within else None}}
+    print(json.dumps(res))
+    return res
+
+
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     if a.scale != 1:
@@ -75,6 +162,8 @@ def main(argv=None) -> dict:
     if not torch.cuda.is_available():
         raise SystemExit("evaluate: needs a HIP device")
     device = torch.device("cuda", torch.cuda.current_device())
+    if a.per_iter:
+        return per_iter(a, device)
     if a.pred_file is not None:
         pred = np.squeeze(np.load(a.pred_file))
         if pred.ndim != 2:

@@ -1403,3 +1403,96 @@ def gt_decode(gt_u8: Tensor, gt_scale: float = 1000.0) -> Tensor:
     out = torch.empty((B, H, W), device=gt_u8.device, dtype=torch.float32)
     _lib.check(_lib.load().fsmi_gt_decode(_p(gt_u8), _p(out), B, H, W, float(gt_scale), _stream(gt_u8)), "gt_decode")
     return out
+
+
+# ---------------------------------------------------------------- scoring a sequence of disparity maps
+
+SEQ_NACC = 14               # FSMI_SEQ_NACC
+SEQ_MAX_ROWS = 64           # FSMI_SEQ_MAX_ROWS
+
+
+def seq_metrics_blocks(H: int, W: int, R: int) -> int:
+    """Partial rows per (pair, prediction row) of the sequence pass (a function of its arguments only)."""
+    return int(_lib.load().fsmi_seq_metrics_blocks(int(H), int(W), int(R)))
+
+
+def _per_row(name: str, what: str, v, R: int, default: float):
+    if v is None:
+        return [float(default)] * R
+    if isinstance(v, (int, float)):
+        return [float(v)] * R
+    v = [float(x) for x in v]
+    if len(v) != R:
+        raise RuntimeError(f"seq_metrics: {len(v)} {what} for {R} rows")
+    return v
+
+
+def seq_metrics(preds, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.0), max_disparity=float("inf"),
+                beta: float = 1.0, weights=None, smooth_rows=(), muls=None, gt_scale: float = 1000.0):
+    """train/losses.py:379-498 (and :20-187) for a whole sequence, in one streaming launch per 32 rows and
+    one finalize, without a host synchronisation.  preds: R <= 64 fp32 maps (B,h_r,w_r); a map whose size
+    differs from the ground truth's is sampled bilinearly (F.interpolate, align_corners=False) as it is
+    read.  Views go in as they are (any batch and line stride); only a map whose innermost stride is not
+    1 is copied.  gt, mask, thresholds, gt_scale: as ``disp_metrics``.  Per row: a factor ``muls`` (1),
+    a clamp to [0, ``max_disparity``] (a float for all rows or one per row; +inf: no clamp at either
+    end), a loss weight ``weights`` (1) and whether the row enters the loss by its smooth-L1 mean
+    (``smooth_rows``, with ``beta``) or its EPE -> (table (B,R,14) fp64, sums (B,R,14) fp64, loss (B)
+    fp64).  include/fsmi.h has the layout of the rows and the arithmetic."""
+    preds = list(preds)
+    R = len(preds)
+    if not 1 <= R <= SEQ_MAX_ROWS:
+        raise RuntimeError(f"seq_metrics: {R} rows, 1..{SEQ_MAX_ROWS}")
+    _check("seq_metrics", *preds)
+    if not isinstance(gt, torch.Tensor):
+        raise TypeError("seq_metrics: expected tensors")
+    u8 = gt.dtype == torch.uint8
+    (_check_u8 if u8 else _check)("seq_metrics", gt)
+    if gt.dim() != (4 if u8 else 3) or (u8 and gt.shape[3] != 3):
+        raise RuntimeError(f"seq_metrics: gt must be fp32 (B,H,W) or uint8 (B,H,W,3), got {gt.dtype} {tuple(gt.shape)}")
+    B, H, W = gt.shape[:3]
+    dev = gt.device
+    for r, p in enumerate(preds):
+        if p.dim() != 3 or p.shape[0] != B or p.shape[1] < 1 or p.shape[2] < 1 or p.device != dev:
+            raise RuntimeError(f"seq_metrics: row {r} must be ({B},h,w) on the device of gt, got {tuple(p.shape)}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("seq_metrics: mask must be a bool or uint8 tensor")
+        _check_u8("seq_metrics", mask.view(torch.uint8))
+        if tuple(mask.shape) != (B, H, W) or mask.device != dev:
+            raise RuntimeError(f"seq_metrics: mask must be ({B},{H},{W}) on the device of gt, got {tuple(mask.shape)}")
+        mask = mask.contiguous().view(torch.uint8)
+    thr = [float(t) for t in thresholds]
+    if len(thr) > METRICS_MAX_THRESHOLDS:
+        raise RuntimeError(f"seq_metrics: {len(thr)} thresholds, at most {METRICS_MAX_THRESHOLDS}")
+    if u8 and not float(gt_scale) > 0.0:
+        raise RuntimeError(f"seq_metrics: gt_scale = {gt_scale} must be positive")
+    if not float(beta) >= 0.0:
+        raise RuntimeError(f"seq_metrics: beta = {beta} must not be negative")
+    maxd = _per_row("seq_metrics", "max_disparity values", max_disparity, R, float("inf"))
+    if any(m != m for m in maxd):
+        raise RuntimeError("seq_metrics: max_disparity is NaN")
+    w = _per_row("seq_metrics", "weights", weights, R, 1.0)
+    mul = _per_row("seq_metrics", "muls", muls, R, 1.0)
+    smooth = [0] * R
+    for r in smooth_rows:
+        if not 0 <= int(r) < R:
+            raise RuntimeError(f"seq_metrics: smooth row {r} of {R} rows")
+        smooth[int(r)] = 1
+    # a view keeps its strides; a copy only where a line is not dense or runs backwards
+    preds = [p if p.stride(2) == 1 and p.stride(1) >= p.shape[2] and p.stride(0) >= 0 else p.contiguous() for p in preds]
+    gt = gt.contiguous()
+    lib = _lib.load()
+    NB = seq_metrics_blocks(H, W, R)
+    partials = torch.empty((B, R, NB, SEQ_NACC), device=dev, dtype=torch.float64)
+    sums = torch.empty((B, R, SEQ_NACC), device=dev, dtype=torch.float64)
+    table = torch.empty((B, R, SEQ_NACC), device=dev, dtype=torch.float64)
+    loss = torch.empty((B,), device=dev, dtype=torch.float64)
+    LL, CI, CF, CD = ctypes.c_longlong * R, ctypes.c_int * R, ctypes.c_float * R, ctypes.c_double * R
+    rows, _keep = _lib.ptr_array([_p(p) for p in preds])
+    cthr = (ctypes.c_float * max(len(thr), 1))(*thr)        # rounded to fp32 here, compared in fp32
+    _lib.check(lib.fsmi_seq_metrics(rows, LL(*[p.stride(0) for p in preds]), LL(*[p.stride(1) for p in preds]),
+                                    CI(*[p.shape[1] for p in preds]), CI(*[p.shape[2] for p in preds]), CF(*mul),
+                                    CF(*maxd), CD(*w), bytes(smooth), R, None if u8 else _p(gt), _p(gt) if u8 else None,
+                                    _p(mask) if mask is not None else None, cthr, len(thr), float(gt_scale), float(beta),
+                                    _p(partials), _p(sums), _p(table), _p(loss), B, H, W, _stream(gt)), "seq_metrics")
+    return table, sums, loss

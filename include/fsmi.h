@@ -503,6 +503,56 @@ int fsmi_disp_metrics(const float* pred, const float* gt, const unsigned char* g
  * aligned, the arithmetic above (bit-equal to float32 of the reference's float64 decode). */
 int fsmi_gt_decode(const unsigned char* gt_u8, float* out, int B, int H, int W, double gt_scale, void* stream);
 
+/* ---- scoring a sequence of disparity maps: every refinement iteration in one pass ----
+ * R <= FSMI_SEQ_MAX_ROWS prediction maps ("rows") of one batch against one ground truth: per (pair,
+ * row) EPE, RMSE, smooth-L1, bad-pixel rates and D1, and per pair the weighted sequence loss; replaces
+ * foundation_stereo_loss and the single-map losses beside it (train/losses.py:20-187, :379-498), which
+ * gather through a boolean mask once per map, resize with F.interpolate and read about 7 scalars back
+ * per map.  Like the stage above: no host synchronisation, no allocation, no float atomics, capturable.
+ *
+ * Row r is an fp32 map (B, hs[r], ws[r]) given by its base pointer rows[r] (4-byte aligned; device
+ * memory), the stride between pairs batch_strides[r] and between lines row_strides[r] (in elements,
+ * row_strides[r] >= ws[r]; the element stride is 1): views such as padder.unpad's go in as they are.
+ * The nine per-row arrays (rows .. smooth) are R values each in HOST memory, read before the call
+ * returns.  gt, gt_u8, mask, thresholds, gt_scale and validity are fsmi_disp_metrics's, except that gt
+ * needs 4-byte and gt_u8 / mask 1-byte alignment only.  Per VALID pixel (y, x) and row r, in
+ * un-contracted fp32 as torch evaluates it:
+ *   1. v = row[y][x] when (hs[r], ws[r]) == (H, W); otherwise the bilinear sample of
+ *      F.interpolate(align_corners=False): per axis, with s = (float)in / (float)out rounded once on
+ *      the host,  src = max(s * (dst + 0.5f) - 0.5f, 0);  i0 = min((int)src, in - 1);
+ *      i1 = min(i0 + 1, in - 1);  l1 = src - i0;  l0 = 1 - l1;  then
+ *      v = l0y * (l0x * p00 + l1x * p01) + l1y * (l0x * p10 + l1x * p11)
+ *   2. v = v * muls[r]
+ *   3. max_disps[r] < +inf:  v = v < 0 ? 0 : v;  v = v > max_disps[r] ? max_disps[r] : v  (torch.clamp:
+ *      a NaN stays NaN).  max_disps[r] = +inf: no clamp at either end.
+ *   4. e = fabsf(v - gt)
+ *   5. sl1 = beta == 0 ? e : (e < beta ? (0.5f * (e * e)) / beta : e - 0.5f * beta)   (IEEE division)
+ *   bad[k], d1 and nonfinite are counted on e as fsmi_disp_metrics counts them; (double)e,
+ *   (double)e * (double)e and (double)sl1 are what is added.
+ * partials: workspace, (B, R, fsmi_seq_metrics_blocks of (H,W,R), FSMI_SEQ_NACC) fp64; every row is
+ * written, none is read before it is.  sums, table: (B, R, FSMI_SEQ_NACC) fp64; loss: (B) fp64.
+ *   sums[b][r]  = [n_valid, sum e, sum e^2, sum sl1, n_d1, n_nonfinite, n_bad[0..7]]   additive over
+ *                 pairs and calls; counts are exact doubles; unused n_bad slots are 0
+ *   table[b][r] = [n_valid, epe, rmse, smooth_l1, d1_all, n_nonfinite, bad[0..7]]   means and rates over
+ *                 n_valid, rmse = sqrt(sum e^2 / n); n_valid == 0 gives zeros (train/losses.py:60)
+ *   loss[b]     = sum over r, added in row order in fp64 without contraction, of
+ *                 weights[r] * (smooth[r] ? table[b][r].smooth_l1 : table[b][r].epe)
+ *                 (row 0 = the initial disparity, smooth, weight 1, and rows 1..K = the iterations with
+ *                 weights gamma^(K-k): foundation_stereo_loss's total_loss)
+ * Order of the additions: a block adds its pixels lane by lane in index order and reduces by a fixed
+ * shuffle tree; the finalize kernel (one block per pair, once per call) adds the blocks' partial rows
+ * in index order and finishes with the same tree.  It is fixed by (H*W, the block count) alone, and
+ * the block count by (H*W, R) alone: equal inputs give equal bits, run to run and in a graph replay. */
+#define FSMI_SEQ_NACC 14
+#define FSMI_SEQ_MAX_ROWS 64
+/* Partial rows per (pair, prediction row) of the streaming pass: a function of its arguments only; >= 1. */
+int fsmi_seq_metrics_blocks(int H, int W, int R);
+int fsmi_seq_metrics(const float* const* rows, const long long* batch_strides, const long long* row_strides,
+                     const int* hs, const int* ws, const float* muls, const float* max_disps, const double* weights,
+                     const unsigned char* smooth, int R, const float* gt, const unsigned char* gt_u8,
+                     const unsigned char* mask, const float* thresholds, int K, double gt_scale, float beta,
+                     double* partials, double* sums, double* table, double* loss, int B, int H, int W, void* stream);
+
 /* ---- live kernel timing (bench.py roofline) -----------------------------
  * When enabled, every launch of the kernels below is bracketed by a pair of
  * hipEvents recorded on the launch stream (skipped while the stream is being

@@ -346,9 +346,61 @@ def metrics():
     print("metrics_small", {k: (v.shape, v.dtype) for k, v in g.items()}, keys)
 
 
+def seq():
+    """foundation_stereo_loss and the three single-map losses (train/losses.py:20-187, :379-498) run by
+    the reference, pair by pair, on tests/seq_oracle.py golden_case (hash PRNG): pins the oracle of the
+    sequence metrics.  Two parameter sets, the initial disparity once at 10 x 16 (resized by the
+    reference's own F.interpolate) and once at full size.  The file holds what the reference returned
+    plus checksums of the inputs.  Also enforces the case's condition: at most 2 valid pixels of the
+    resized initial row lie within the resize's rounding gap of a rate threshold."""
+    import_reference()
+    import torch.nn.functional as F
+    ref = _load_by_path("ref_train_losses", "train", "losses.py")
+    from tests import seq_oracle as so
+    case = so.golden_case()
+    gt, mask, preds = case["gt"], case["mask"], case["preds"]
+    B, H, W = gt.shape
+    keys = None
+    g = {"checksums": np.array(so.checksums(case)), "params": np.array(so.GOLDEN_PARAMS)}
+    for pi, (gamma, maxd) in enumerate(so.GOLDEN_PARAMS):
+        for name in ("init_small", "init_full"):
+            for b in range(B):
+                loss, misc = ref.foundation_stereo_loss(t(case[name][b]), [t(p[b]) for p in preds], t(gt[b]),
+                                                        t(mask[b]), gamma=gamma, max_disparity=maxd)
+                keys = keys or sorted(misc)
+                g[f"fsl_p{pi}_{name}_pair{b}"] = np.array([float(loss)] + [misc[k] for k in keys], dtype=np.float64)
+        for b in range(B):
+            last = t(preds[-1][b])
+            outs = [ref.disparity_l1_loss(last, t(gt[b]), t(mask[b]), max_disparity=maxd),
+                    ref.disparity_smooth_l1_loss(last, t(gt[b]), t(mask[b]), beta=0.5, max_disparity=maxd),
+                    ref.disparity_epe_loss(last, t(gt[b]), t(mask[b]), max_disparity=maxd),
+                    ref.disparity_smooth_l1_loss(t(case["init_small"][b]), t(gt[b]), t(mask[b]), beta=1.0,
+                                                 max_disparity=maxd)]
+            g[f"single_p{pi}_pair{b}"] = np.array([[float(l), m["epe"], m["d1_error"], m["d3_error"]] for l, m in outs],
+                                                  dtype=np.float64)
+    g["keys"] = np.array(keys)
+    g["single_keys"] = np.array(["loss", "epe", "d1_error", "d3_error"])
+    # the condition of the resized row's rate bound (tests/test_seq_host.py)
+    up = F.interpolate(t(case["init_small"])[:, None], size=(H, W), mode="bilinear", align_corners=False)[:, 0].numpy()
+    mine = so.upsample(case["init_small"], H, W)
+    measured, gap = float(np.abs(up - mine).max()), so.resize_gap_bound(np.abs(case["init_small"]).max())
+    assert measured <= gap, (measured, gap)
+    for _, maxd in so.GOLDEN_PARAMS:
+        e = np.abs(so.row_values(case["init_small"], H, W, 1.0, maxd) - gt)[mask]
+        M = int(((np.abs(e - 1.0) <= gap) | (np.abs(e - 3.0) <= gap)).sum())
+        assert M <= 2, f"{M} pixels within {gap} of a threshold: change seq_oracle.GOLDEN_TAG"
+    np.savez_compressed(os.path.join(OUT, "seq_small.npz"), **g)
+    print("seq_small", {k: (v.shape, v.dtype) for k, v in g.items()}, keys, "resize gap", measured, "bound", gap)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud", "frames", "metrics"]
+    which = sys.argv[1:] or ["ops", "update", "e2e", "hiera", "backbone", "cloud", "frames", "metrics", "seq"]
+    if "seq" in which:
+        seq()
+        which = [w for w in which if w != "seq"]
+        if not which:
+            return
     if "cloud" in which:
         cloud()
     if "frames" in which:
