@@ -98,6 +98,7 @@ SIGNATURES = {
     "fsmi_timer_release_captured": [],
     "fsmi_timer_dump_captured": [ctypes.c_char_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)],
     "fsmi_timer_captured_count": [ctypes.POINTER(ctypes.c_longlong)],
+    "fsmi_stream_capture_id": [_P, ctypes.POINTER(ctypes.c_longlong)],
 }
 
 KERNELS = ["gwc", "concat", "comb", "proj", "corr", "volpyr", "lookup", "sampler", "reg", "upsample",

@@ -212,6 +212,19 @@ const char* fsmi_last_error(void) { return fsmi::g_err.c_str(); }
 
 const char* fsmi_arch(void) { return "gfx950"; }
 
+int fsmi_stream_capture_id(void* stream, long long* id) {
+  FSMI_CHECK_ARG(id, "fsmi_stream_capture_id: null pointer");
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  unsigned long long cid = 0;
+  hipError_t e = hipStreamGetCaptureInfo(static_cast<hipStream_t>(stream), &st, &cid);
+  if (e != hipSuccess) {
+    fsmi::set_error("fsmi_stream_capture_id: %s", hipGetErrorString(e));
+    return static_cast<int>(e);
+  }
+  *id = st == hipStreamCaptureStatusActive ? static_cast<long long>(cid) : -1;
+  return FSMI_OK;
+}
+
 int fsmi_timer_enable(int on) {
   std::lock_guard<std::mutex> lk(fsmi::g_mu);
   fsmi::g_enabled = on != 0;

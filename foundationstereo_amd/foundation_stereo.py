@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, streams
 from . import submodule as _sub
 from . import update as _update
 from .backbone import Feature
@@ -34,7 +34,7 @@ from .geometry import Combined_Geo_Encoding_Volume
 from .submodule import (BasicConv, BasicConv_IN, ChannelAttentionEnhancement, Conv2x, Conv3dNormActReduced,
                         CostVolumeDisparityAttention, FeatureAtt, ResnetBasicBlock3D, SpatialAttentionExtractor,
                         build_concat_volume, build_gwc_volume)
-from .update import BasicSelectiveMultiUpdateBlock, stream_wait
+from .update import BasicSelectiveMultiUpdateBlock
 from .utils import InputPadder
 
 _MEAN = (0.485, 0.456, 0.406)
@@ -63,7 +63,8 @@ _NORM_CACHE = {}
 # (see forward); FSMI_RANGE_GUARD=0, or a caller that checks ops.check_range() itself and sets the
 # attribute, leaves the flag to the caller.  update.OVERLAP (bench.py) also decides whether the context
 # net (+ stem_2, CAM / SAM), the FeatureAtt gates and the hourglass's disparity-transformer branch run on
-# side streams beside the 3D path.
+# side streams beside the 3D path; they fork and join through streams.py (fork / join), which names the
+# streams and checks every wait under capture (capture_fork).
 RANGE_GUARD = os.environ.get("FSMI_RANGE_GUARD", "1") != "0"
 
 
@@ -131,10 +132,9 @@ class hourglass(nn.Module):
         if _update.OVERLAP and self._dt_fast(x, x):
             # the disparity transformer branch (patch embed + 4 encoder layers, ~0.45 ms at cfg2, a few
             # hundred waves) reads only x: it runs on a side stream beside conv1 .. conv1_up
-            main = torch.cuda.current_stream(x.device)
-            dt_s = _update._side_stream(x.device, 1)
-            stream_wait(dt_s, main)
-            with torch.cuda.stream(dt_s):
+            main = streams.current(x.device)
+            dt_s = streams.side(x.device, streams.BRANCH)
+            with streams.fork(dt_s, main):
                 scale, shift = self._patch_fold()
                 t = self.atts["4"](ops.dt_patch_embed(_sub._f32(x), self.conv_patch[0].weight.float(), scale, shift))
         if _sub.FATT_FUSE and not self.training:
@@ -154,11 +154,10 @@ class hourglass(nn.Module):
             c1 = self.feature_att_up_8(self.agg_1(torch.cat((self.conv2_up(c2), c1), dim=1)), features[1])
         conv = self.conv1_up(c1)
         if dt_s is not None and tuple(conv.shape) == tuple(x.shape):
-            stream_wait(main, dt_s)
-            t.record_stream(main)
+            streams.join(main, dt_s, t)
             return self.conv_out(ops.upsample4_add_(conv.float().contiguous(), t))
         if dt_s is not None:
-            stream_wait(main, dt_s)
+            streams.join(main, dt_s)
         if self._dt_fast(x, conv):
             # patch embed, transformer and the x4 trilinear add on HIP (csrc/transformer.hip)
             scale, shift = self._patch_fold()
@@ -319,8 +318,7 @@ class FoundationStereo(nn.Module):
             return self._forward(image1, image2, iters, flow_init, test_mode, low_memory, init_disp)
         if not (image1.is_cuda and RANGE_GUARD):
             return run()
-        if torch.cuda.is_current_stream_capturing():
-            _update._CAPTURE_EDGES.clear()          # capture_fork: this forward's waits only
+        if streams.capturing():
             # a captured forward cannot synchronise: its last node NaN-fills the disparity when the
             # flag is set, so a replay that overflowed never returns a finite result (ShardedStereo
             # reads the flag after a replay and recovers)
@@ -350,10 +348,9 @@ class FoundationStereo(nn.Module):
                                                                      self.args.corr_levels)
                 # stem_2 + context net + CAM / SAM read only the images and vit_feat: a side stream
                 # runs them beside the volume build and the 3D filtering (joined before the loop)
-                main = torch.cuda.current_stream(image1.device)
-                ctx_s = _update._side_stream(image1.device, 0)
-                stream_wait(ctx_s, main)
-                with torch.cuda.stream(ctx_s):
+                main = streams.current(image1.device)
+                ctx_s = streams.side(image1.device, streams.MOTION)
+                with streams.fork(ctx_s, main):
                     stem_2x, net_list, inp_list, att = self._context(image1, vit_feat)
                     ctx_pre = self.update_block.context_pre(inp_list)
             else:
@@ -364,13 +361,11 @@ class FoundationStereo(nn.Module):
             if fuse and ctx_s is not None:
                 # the six FeatureAtt gates (2D 1x1 convs on the features) on a side stream, ready long
                 # before the volume convs that apply them; an event joins only them
-                g_s = _update._side_stream(image1.device, 1)
-                stream_wait(g_s, main)
-                with torch.cuda.stream(g_s):
+                g_s = streams.side(image1.device, streams.BRANCH)
+                with streams.fork(g_s, main):
                     gates = (self.corr_feature_att.logits(features_left[0]),) + \
                         self.cost_agg.gate_logits(features_left)
-                    g_ev = torch.cuda.Event()
-                    g_ev.record(g_s)
+                    g_ev = streams.record(g_s)
             if not ctx_overlap:
                 vol = self.build_stem_volume(features_left[0], features_right[0])
             if fuse:
@@ -379,9 +374,7 @@ class FoundationStereo(nn.Module):
                 for m in list(self.corr_stem)[1:-1]:
                     vol = m(vol)
                 if gates is not None:
-                    main.wait_event(g_ev)
-                    for t in gates:
-                        t.record_stream(main)
+                    streams.join(main, g_s, *gates, event=g_ev)
                 g0 = gates[0] if gates is not None else self.corr_feature_att.logits(features_left[0])
                 vol = self.corr_stem[-1](vol, fatt=g0)
             else:
@@ -402,9 +395,7 @@ class FoundationStereo(nn.Module):
                                            head.bias.float()).squeeze(1)
                 init_disp = ops.softmax_regression(logits)
             if ctx_s is not None:
-                stream_wait(main, ctx_s)
-                for t in [stem_2x, *net_list, *inp_list, *att, *(ctx_pre or ())]:
-                    t.record_stream(main)
+                streams.join(main, ctx_s, stem_2x, *net_list, *inp_list, *att, *(ctx_pre or ()))
 
         if geo_fn is None:
             geo_fn = Combined_Geo_Encoding_Volume(features_left[0].float(), features_right[0].float(), vol.float(),

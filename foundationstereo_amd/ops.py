@@ -1008,6 +1008,14 @@ def timer_captured_count():
     return n.value
 
 
+def stream_capture_id(stream: int):
+    """Id of the hipGraph capture the stream (a HIP handle) is part of, None when it is not capturing."""
+    import ctypes
+    cid = ctypes.c_longlong(-1)
+    _lib.check(_lib.load().fsmi_stream_capture_id(stream, ctypes.byref(cid)), "stream_capture_id")
+    return cid.value if cid.value >= 0 else None
+
+
 def timer_release_captured():
     """Forget the clock records of captured launches and free their slots; only once every graph
     captured with ``in_capture=True`` is destroyed (include/fsmi.h)."""

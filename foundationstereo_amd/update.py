@@ -25,15 +25,17 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, streams
 from .submodule import EdgeNextConvEncoder, _cached, _f32, _hip
 
 # What still switches a path here, and who uses it:
 #   CONV_ENGINE     "miopen" forces the torch path (bench.py --conv-engine)
 #   OVERLAP         side streams for the motion path, the GRU small branches, the mask head and the gru16 /
-#                   gru08 pipeline (FSMI_OVERLAP; bench.py)
-#   PIPE_BRANCH     run_pipelined: gru04's small branch on its own stream (FSMI_PIPE_BRANCH;
-#                   tests/test_gpu_capture_fork.py)
+#                   gru08 pipeline (FSMI_OVERLAP; bench.py).  The streams, and every fork / join / wait
+#                   between them, are streams.py's; whether a SelectiveConvGRU forks its small branch is
+#                   its caller's ``fork_small`` argument
+#   PIPE_BRANCH     run_pipelined: gru04's small branch on its own stream, i.e. its ``fork_small``
+#                   (FSMI_PIPE_BRANCH; tests/test_gpu_capture_fork.py)
 #   MOTION_ON_MAIN  run_pipelined: the motion path (lookup + encoder) on the main stream instead of the
 #                   motion stream (FSMI_MOTION_ON_MAIN; tests/test_gpu_capture_fork.py)
 #   CTX_PRE         SelectiveConvGRU.conv0's context segment convolved once per forward (context_pre);
@@ -82,97 +84,6 @@ def _packed(*mods, cin_order=None):
 
     slot = "_fsmi_pack" if cin_order is None else f"_fsmi_pack_{tuple(cin_order)}"
     return _cached(mods[0], slot, [t for m in mods for t in (m.weight, m.bias)], build)
-
-
-_SIDE = {}
-
-
-def _side_stream(device, idx=0):
-    """Side stream ``idx`` of ``device`` (0: motion path, 1: GRU small branches / mask head, 3: the
-    gru16 / gru08 pipeline of ``run_pipelined``)."""
-    s = _SIDE.get((device, idx))
-    if s is None:
-        # all at default priority: ANY side stream at high priority -- motion (round 4), the branch or
-        # the pipeline stream (round 5) -- measured 14.5-14.7 vs 19.0-20.9 pairs/s
-        s = _SIDE[(device, idx)] = torch.cuda.Stream(device=device)
-    return s
-
-
-# capture_fork -- the rule every fork / join of a side stream here follows under hipGraph capture:
-# a side stream waits only on the capture's origin stream (or on a stream that never waits on it in
-# turn); it may be waited on by any stream, and is joined back by the origin.  On this ROCm (HIP 7,
-# torch 2.10) a side stream X that waits on side stream A which later waits on X (a fork from a side
-# stream plus its join) makes hipStreamEndCapture segfault: tools/capture_fork_probe.py reproduces it
-# with plain torch ops (variants a_only, two_parents, enter_main_wait_side segfault; main_only,
-# via_main pass).  Hence gru08's small branch on the pipeline stream runs in order, and the motion
-# path's disparity branch forks from main, not from the motion stream.
-#
-#
-# Enforced by ``stream_wait`` (every wait between streams here goes through it): while a capture is in
-# progress it records the waits between side streams and raises before a wait that would close a cycle
-# (X waiting on A after A waited on X, directly or through other side streams) -- every variant the
-# probe saw segfault has such a mutual wait, every variant that passed has none.
-_CAPTURE_EDGES = {}          # key(waiter) -> set of key(waited), side streams only, current capture
-
-
-def _skey(s):
-    """A stream's identity: its HIP handle (torch.cuda.current_stream() returns a new Python wrapper on
-    every call, so id() of the wrapper does not identify the stream); id() for handle-less stand-ins."""
-    h = getattr(s, "cuda_stream", None)
-    return ("hip", h) if h is not None else ("obj", id(s))
-
-
-class CaptureForkError(RuntimeError):
-    """A stream wait that would make hipStreamEndCapture segfault on this ROCm (capture_fork)."""
-
-
-def capture_fork_check(waiter, waited, capturing: bool, side_ids=None):
-    """Record ``waiter`` waiting on ``waited`` for the capture in progress; raise CaptureForkError when
-    ``waited`` already (transitively) waits on ``waiter``.  Only edges between side streams count (the
-    capture origin forks and joins every side stream).  ``side_ids``: ``_skey`` of the side streams (default
-    the ones ``_side_stream`` made).  Not capturing: forget the edges (a new capture starts clean)."""
-    if not capturing:
-        _CAPTURE_EDGES.clear()
-        return
-    side = side_ids if side_ids is not None else {_skey(v) for v in _SIDE.values()}
-    a, b = _skey(waiter), _skey(waited)
-    if a == b or a not in side or b not in side:
-        return
-    seen, todo = set(), [b]
-    while todo:                                  # does `waited` reach `waiter` through recorded waits?
-        x = todo.pop()
-        if x == a:
-            raise CaptureForkError("capture_fork: a side stream would wait on a side stream that already waits "
-                                   "on it inside this hipGraph capture (hipStreamEndCapture segfaults on this "
-                                   "ROCm; tools/capture_fork_probe.py) -- fork from the capture origin instead")
-        if x not in seen:
-            seen.add(x)
-            todo.extend(_CAPTURE_EDGES.get(x, ()))
-    _CAPTURE_EDGES.setdefault(a, set()).add(b)
-
-
-# diagnostics (tools/replay_timeline.py): while a list, every wait issued during a capture is logged as
-# (waiter stream handle, waited stream handle, number of clocked launches captured so far), which with
-# the capture-ordered clock records gives the captured graph's cross-stream edges
-WAIT_LOG = None
-
-
-def stream_wait(waiter, waited):
-    """``waiter.wait_stream(waited)`` with the capture_fork check while a capture is in progress."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    capture_fork_check(waiter, waited, capturing)
-    if WAIT_LOG is not None and capturing:
-        WAIT_LOG.append((waiter.cuda_stream, waited.cuda_stream, ops.timer_captured_count()))
-    waiter.wait_stream(waited)
-
-
-# side stream the SelectiveConvGRU small branch forks to (1); 0: the branches run in order on the
-# caller's stream (run_pipelined: the pipeline stream is itself a side stream, see capture_fork)
-_BRANCH = [1]
-
-
-def _branch_stream(device):
-    return _side_stream(device, _BRANCH[0])
 
 
 def _conv(mods, segs, act=None, **kw):
@@ -386,9 +297,10 @@ class SelectiveConvGRU(nn.Module):
         pk, _ = _packed(self.conv0[0], cin_order=tuple(order))
         return ops.conv2d(ss, pk, act="relu_pre", res=pre)
 
-    def forward(self, att, h, *x, pre=None):
+    def forward(self, att, h, *x, pre=None, fork_small=True):
         """``pre``: ``context_pre(x[0])`` of this forward's context feature (HIP path; x[0] is then not read;
-        the torch path ignores it, its conv0 takes the whole cat)."""
+        the torch path ignores it, its conv0 takes the whole cat).  ``fork_small``: with ``OVERLAP`` the small
+        branch runs on the branch stream; False (a caller on a side stream, streams.py capture_fork): in order."""
         if _fast(h):
             h = _f32(h)
             if pre is not None:
@@ -418,20 +330,18 @@ class SelectiveConvGRU(nn.Module):
                 pk, b, z, rh = branch(sg, "blend_small")
                 ops.conv2d_gate([rh, xc], pk, b, "blend_small", h=h, z=z, att=att, out=out)
 
-            if OVERLAP and _BRANCH[0]:
+            if OVERLAP and fork_small:
                 # small (1x1) branch on a side stream beside the large branch's zr conv; the
                 # large blend adds into ``out`` after the small blend has written it
-                main = torch.cuda.current_stream(h.device)
-                side = _branch_stream(h.device)
-                stream_wait(side, main)
-                with torch.cuda.stream(side):
+                main = streams.current(h.device)
+                side = streams.side(h.device, streams.BRANCH)
+                with streams.fork(side, main):
                     small()
                 pk, b, z, rh = branch(self.large_gru, "blend_large")
-                stream_wait(main, side)
-                ops.conv2d_gate([rh, xc], pk, b, "blend_large", h=h, z=z, att=att, out=out)
-                return out
-            small()
-            pk, b, z, rh = branch(self.large_gru, "blend_large")
+                streams.join(main, side)
+            else:
+                small()
+                pk, b, z, rh = branch(self.large_gru, "blend_large")
             ops.conv2d_gate([rh, xc], pk, b, "blend_large", h=h, z=z, att=att, out=out)
             return out
         x = torch.cat(x, dim=1) if len(x) > 1 else x[0]
@@ -498,15 +408,27 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
         Cross-stream buffers (``enc``) are allocated on the calling stream and ``disp`` is only
         released by the caller after the join, so the caching allocator never recycles memory a
         pending side-stream kernel still reads.  Captures into a hipGraph as a fork/join."""
-        main = torch.cuda.current_stream(disp.device)
-        side = _side_stream(disp.device)
+        main = streams.current(disp.device)
+        s_mot, s_br = streams.side(disp.device, streams.MOTION), streams.side(disp.device, streams.BRANCH)
         B, _, H, W = disp.shape
         enc = disp.new_empty(B, self.encoder.conv.out_channels + 1, H, W)
-        stream_wait(side, main)
-        with torch.cuda.stream(side):
+        with streams.fork(s_mot, main):
             self.encoder.motion_into(disp, geo_fn, enc)
-        n = self.args.n_gru_layers
         p0, p1, p2 = (list(pre) + [None] * 3)[:3] if pre is not None else (None, None, None)
+        self._coarse_grus(net, inp, att, p1, p2)
+        streams.join(main, s_mot)
+        if self.args.n_gru_layers > 1:
+            net[0] = self.gru04(att[0], net[0], inp[0], enc, interp(net[1], net[0]), pre=p0)
+        # mask head beside the disparity head (both read net[0] only)
+        with streams.fork(s_br, main):
+            mask = self._mask_head(net[0])
+        delta_disp = self.disp_head(net[0])
+        streams.join(main, s_br)
+        return net, mask, delta_disp
+
+    def _coarse_grus(self, net, inp, att, p1=None, p2=None):
+        """gru16, then gru08, of one iteration (HIP path), written into ``net``; ``p1`` / ``p2``: their context_pre."""
+        n = self.args.n_gru_layers
         if n == 3:
             net[2] = self.gru16(att[2], net[2], inp[2], pool2x(net[1]), pre=p2)
         if n >= 2:
@@ -514,17 +436,10 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
                 net[1] = self.gru08(att[1], net[1], inp[1], pool2x(net[0]), interp(net[2], net[1]), pre=p1)
             else:
                 net[1] = self.gru08(att[1], net[1], inp[1], pool2x(net[0]), pre=p1)
-        stream_wait(main, side)
-        if n > 1:
-            net[0] = self.gru04(att[0], net[0], inp[0], enc, interp(net[1], net[0]), pre=p0)
-        # mask head beside the disparity head (both read net[0] only)
-        side1 = _side_stream(disp.device, 1)
-        stream_wait(side1, main)
-        with torch.cuda.stream(side1):
-            mask = _conv(self.mask[2], [_conv(self.mask[0], [net[0]], "relu")], "relu", alpha=0.25)
-        delta_disp = self.disp_head(net[0])
-        stream_wait(main, side1)
-        return net, mask, delta_disp
+
+    def _mask_head(self, n0):
+        """0.25 * mask(n0) on the HIP path (the scale in the last conv's epilogue)."""
+        return _conv(self.mask[2], [_conv(self.mask[0], [n0], "relu")], "relu", alpha=0.25)
 
     def run_pipelined(self, net, inp, geo_fn, disp, att, iters, pre=None):
         """``iters`` refinement iterations (``disp += forward(net, inp, geo_fn(disp), disp, att)[2]``
@@ -536,7 +451,7 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
         disp(t+1)).  The critical path per iteration is gru04 + max(head + motion, gru08) instead of
         gru16 + gru08 + gru04 + head.  Every value is computed by the same kernels from the same
         inputs as ``forward`` (bit-identical); only the order of independent work changes.
-        One pipeline stream and whole-stream joins: ``stream_wait(main, s_gru)`` is issued after
+        One pipeline stream and whole-stream joins: ``join(main, s_gru)`` is issued after
         gru08(t) and before gru16(t+1) is enqueued, so gru04(t) waits for the former only.  The
         mask head shares the motion stream.  A tensor read on another stream is freed only after
         the freeing stream has joined the reader, so the caching allocator never recycles memory
@@ -544,19 +459,17 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
         iteration only (test mode discards the others).  ``pre``: ``context_pre(inp)`` (loop-invariant
         conv0 parts per level) or None."""
         dev = disp.device
-        main = torch.cuda.current_stream(dev)
-        s_mot, s_gru = _side_stream(dev, 0), _side_stream(dev, 3)
+        main = streams.current(dev)
+        s_mot, s_gru = streams.side(dev, streams.MOTION), streams.side(dev, streams.PIPELINE)
         n0, n1, n2 = net
         p0, p1, p2 = pre if pre is not None else (None, None, None)
         B, _, H, W = disp.shape
-        main_branch = PIPE_BRANCH                        # gru04's small branch on stream 1 (4th stream)
         nc = self.encoder.conv.out_channels
-        stream_wait(s_gru, main)
-        _BRANCH[0] = 0                                   # pipeline-stream GRUs: branches in order
-        with torch.cuda.stream(s_gru):
-            n2 = self.gru16(att[2], n2, inp[2], pool2x(n1), pre=p2)
-            n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), interp(n2, n1), pre=p1)
-        _BRANCH[0] = 1
+        # fork_small=False for every GRU on the pipeline stream: its branches run in order there -- a fork
+        # from it would be a side stream waiting on the pipeline stream and waited on by it (capture_fork)
+        with streams.fork(s_gru, main):
+            n2 = self.gru16(att[2], n2, inp[2], pool2x(n1), pre=p2, fork_small=False)
+            n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), interp(n2, n1), pre=p1, fork_small=False)
         mask = None
         # the disparity lives in the last channel of the encoder output it feeds: the disparity head
         # writes disp + delta straight into the next iteration's buffer (no cat copy, no add pass)
@@ -567,37 +480,27 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
             if MOTION_ON_MAIN:
                 self.encoder.motion_into(disp, geo_fn, enc)
             else:
-                stream_wait(s_mot, main)
-                with torch.cuda.stream(s_mot):
+                with streams.fork(s_mot, main):
                     self.encoder.motion_into(disp, geo_fn, enc)
-            stream_wait(main, s_gru)                      # gru08(t): enqueued last on s_gru so far
+            streams.join(main, s_gru)                     # gru08(t): enqueued last on s_gru so far
             if not MOTION_ON_MAIN:
-                stream_wait(main, s_mot)                  # motion(t)
+                streams.join(main, s_mot)                 # motion(t)
             if t + 1 < iters:
-                _BRANCH[0] = 0
-                with torch.cuda.stream(s_gru):           # gru16(t+1), beside gru04(t)
-                    n2 = self.gru16(att[2], n2, inp[2], pool2x(n1), pre=p2)
+                with streams.on(s_gru):                  # gru16(t+1), beside gru04(t): behind gru08(t), no wait
+                    n2 = self.gru16(att[2], n2, inp[2], pool2x(n1), pre=p2, fork_small=False)
                     # gru08(t+1)'s upsampled gru16 input, also beside gru04(t): one kernel less between
                     # gru04(t) and gru08(t+1)
                     up2 = interp(n2, n1)
-                _BRANCH[0] = 1
-            _BRANCH[0] = 1 if main_branch else 0
-            n0 = self.gru04(att[0], n0, inp[0], enc, interp(n1, n0), pre=p0)
-            _BRANCH[0] = 1
+            # gru04's small branch on the branch stream (a 4th stream) unless PIPE_BRANCH is off
+            n0 = self.gru04(att[0], n0, inp[0], enc, interp(n1, n0), pre=p0, fork_small=PIPE_BRANCH)
             if t + 1 < iters:
-                stream_wait(s_gru, main)                  # gru04(t)
-                # gru08's branches in order on the pipeline stream: a fork from it would be a side
-                # stream waiting on the pipeline stream and waited on by it (capture_fork)
-                _BRANCH[0] = 0
-                with torch.cuda.stream(s_gru):           # gru08(t+1), beside the heads + motion(t+1)
-                    n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), up2, pre=p1)
-                _BRANCH[0] = 1
+                with streams.fork(s_gru, main):          # gru08(t+1) after gru04(t), beside the heads + motion(t+1)
+                    n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), up2, pre=p1, fork_small=False)
             if t + 1 == iters:
                 # test mode upsamples only the last iteration's disparity: the reference computes the
                 # mask head every iteration and discards all but the last (core/foundation_stereo.py:243-244)
-                stream_wait(s_mot, main)
-                with torch.cuda.stream(s_mot):
-                    mask = _conv(self.mask[2], [_conv(self.mask[0], [n0], "relu")], "relu", alpha=0.25)
+                with streams.fork(s_mot, main):
+                    mask = self._mask_head(n0)
             if t + 1 < iters:
                 enc = disp.new_empty(B, nc + 1, H, W)
                 self.disp_head(n0, res=disp, out=enc, co0=nc)
@@ -605,24 +508,16 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
             else:
                 disp = self.disp_head(n0, res=disp)
             if not MOTION_ON_MAIN or t + 1 == iters:
-                stream_wait(main, s_mot)
-        stream_wait(main, s_gru)
+                streams.join(main, s_mot)
+        streams.join(main, s_gru)
         return [n0, n1, n2], mask, disp
 
     def _forward_fast(self, net, inp, corr, disp, att):
-        n = self.args.n_gru_layers
-        if n == 3:
-            net[2] = self.gru16(att[2], net[2], inp[2], pool2x(net[1]))
-        if n >= 2:
-            if n > 2:
-                net[1] = self.gru08(att[1], net[1], inp[1], pool2x(net[0]), interp(net[2], net[1]))
-            else:
-                net[1] = self.gru08(att[1], net[1], inp[1], pool2x(net[0]))
+        self._coarse_grus(net, inp, att)
         B, _, H, W = corr.shape
         enc = self.encoder.encode_into(disp, corr, corr.new_empty(B, self.encoder.conv.out_channels + 1, H, W))
         # motion = cat([inp[0], enc]) stays two segments of gru04.conv0's input
-        if n > 1:
+        if self.args.n_gru_layers > 1:
             net[0] = self.gru04(att[0], net[0], inp[0], enc, interp(net[1], net[0]))
         delta_disp = self.disp_head(net[0])
-        mask = _conv(self.mask[2], [_conv(self.mask[0], [net[0]], "relu")], "relu", alpha=0.25)
-        return net, mask, delta_disp
+        return net, self._mask_head(net[0]), delta_disp

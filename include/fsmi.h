@@ -611,6 +611,8 @@ int fsmi_timer_dump_captured(char* buf, long long size, long long* needed);
  * without touching the device: callable while a capture is in progress (positions a cross-stream wait
  * among the captured launches; tools/replay_timeline.py). */
 int fsmi_timer_captured_count(long long* n);
+/* *id = the id of the hipGraph capture `stream` is part of (hipStreamGetCaptureInfo), -1 when it is not capturing. */
+int fsmi_stream_capture_id(void* stream, long long* id);
 /* Re-issue the last timed launch of `kernel` (lookup, cost-volume build) `reps` times back to
  * back on its stream between two hipEvents; *avg_ms = span / reps.  The kernels are pure
  * functions of their inputs, so the replays rewrite identical outputs.

@@ -1,10 +1,14 @@
-"""CPU: the capture_fork guard (update.capture_fork_check) against the fork / join patterns of
+"""CPU: the capture_fork guard (streams.capture_fork_check) against the fork / join patterns of
 tools/capture_fork_probe.py -- it must reject exactly the ones that segfaulted hipStreamEndCapture on the
 GPU (profiles/r05_capture_fork_probe.txt) and accept the ones that captured, and the product's own
 pipelined schedule must pass it."""
+import itertools
+
 import pytest
 
-from foundationstereo_amd import update as up
+from foundationstereo_amd import streams as up
+
+_IDS = itertools.count(1000)             # a fresh capture id per replayed pattern
 
 
 class S:                                   # a stream stand-in: identity only (or a HIP handle)
@@ -19,9 +23,9 @@ def run(pattern):
     cur, A, X = S("cur"), S("A"), S("X")
     names = {"cur": cur, "A": A, "X": X}
     side = {up._skey(A), up._skey(X)}
-    up.capture_fork_check(cur, cur, capturing=False)          # a new capture: no edges
+    cid = next(_IDS)                                           # a new capture: no edges
     for w, d in pattern:
-        up.capture_fork_check(names[w], names[d], capturing=True, side_ids=side)
+        up.capture_fork_check(names[w], names[d], cid, side_ids=side)
 
 
 # the probe's variants as waits (waiter, waited), in issue order (tools/capture_fork_probe.py)
@@ -52,9 +56,9 @@ def test_guard_matches_probe(name):
 def test_not_capturing_records_nothing():
     A, X = S("A"), S("X")
     side = {up._skey(A), up._skey(X)}
-    up.capture_fork_check(A, X, capturing=False, side_ids=side)
-    up.capture_fork_check(X, A, capturing=False, side_ids=side)
-    up.capture_fork_check(A, X, capturing=True, side_ids=side)   # fresh capture: fine
+    up.capture_fork_check(A, X, None, side_ids=side)
+    up.capture_fork_check(X, A, None, side_ids=side)
+    up.capture_fork_check(A, X, next(_IDS), side_ids=side)      # fresh capture: fine
 
 
 def test_streams_identified_by_handle():
@@ -62,7 +66,21 @@ def test_streams_identified_by_handle():
     the same stream to the guard (round 6: the guard keyed on id() and missed the real pipeline fork)."""
     A1, A2, X = S("A", handle=0x1000), S("A", handle=0x1000), S("X", handle=0x2000)
     side = {up._skey(A1), up._skey(X)}
-    up.capture_fork_check(A1, X, capturing=False, side_ids=side)
-    up.capture_fork_check(X, A1, capturing=True, side_ids=side)      # X waits on A
+    cid = next(_IDS)
+    up.capture_fork_check(A1, X, None, side_ids=side)
+    up.capture_fork_check(X, A1, cid, side_ids=side)          # X waits on A
     with pytest.raises(up.CaptureForkError):
-        up.capture_fork_check(A2, X, capturing=True, side_ids=side)  # A (another wrapper) waits on X
+        up.capture_fork_check(A2, X, cid, side_ids=side)      # A (another wrapper) waits on X
+
+
+def test_edges_belong_to_one_capture():
+    """An earlier capture's waits are never seen by a later one, with no un-captured call in between
+    (the edges used to be forgotten only by a wait outside capture, or by FoundationStereo.forward on its
+    RANGE_GUARD branch); the same two waits inside one capture are the segfaulting mutual wait."""
+    A, X = S("A"), S("X")
+    side = {up._skey(A), up._skey(X)}
+    up.capture_fork_check(X, A, 1, side_ids=side)             # capture 1: X waits on A
+    up.capture_fork_check(A, X, 2, side_ids=side)             # capture 2: A waits on X -- another graph
+    up.capture_fork_check(X, A, 3, side_ids=side)
+    with pytest.raises(up.CaptureForkError):
+        up.capture_fork_check(A, X, 3, side_ids=side)

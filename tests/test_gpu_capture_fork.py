@@ -7,10 +7,13 @@ under capture must fail this test, not the runner):
   * FSMI_MOTION_ON_MAIN=1: the motion path on the main stream.
 
 Every configuration runs the same kernels on the same inputs, so the eager forward and the replayed
-graph must be bit-identical across all of them.  faulthandler prints the Python stack of a segfault.
+graph must be bit-identical across all of them.  The same child also runs ``forward(test_mode=False)`` --
+the per-iteration loop, update.BasicSelectiveMultiUpdateBlock.forward_overlapped -- eager and captured +
+replayed: its ``init_disp`` and every ``disp_preds[i]`` are held to the same bit equality.  faulthandler
+prints the Python stack of a segfault.
 Forking gru08's small branch from the pipeline stream (round 4's segfault) breaks the capture_fork rule
-(update.py): tools/capture_fork_probe.py reproduces that crash with plain torch ops; update.stream_wait
-now raises CaptureForkError before such a capture can end (tests/test_capture_fork_guard.py, and the
+(streams.py): tools/capture_fork_probe.py reproduces that crash with plain torch ops; streams.wait
+raises CaptureForkError before such a capture can end (tests/test_capture_fork_guard.py, and the
 last test here forces it under a real capture); the middle test runs the probe's passing patterns."""
 import json
 import os
@@ -53,6 +56,19 @@ torch.cuda.synchronize()
 rep = out.float().cpu().numpy()
 np.save(os.environ["OUT"] + "_eager.npy", eager)
 np.save(os.environ["OUT"] + "_graph.npy", rep)
+def seq(res):                       # (init_disp, disp_preds) of test_mode=False
+    return {"init": res[0].float().cpu().numpy(), **{f"pred{i}": p.float().cpu().numpy() for i, p in enumerate(res[1])}}
+with torch.no_grad():
+    eager_seq = seq(model(L, R, iters=iters, test_mode=False))
+    torch.cuda.synchronize()
+    g2 = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g2):
+        out2 = model(L, R, iters=iters, test_mode=False)
+g2.replay()
+g2.replay()
+torch.cuda.synchronize()
+np.savez(os.environ["OUT"] + "_seq_eager.npz", **eager_seq)
+np.savez(os.environ["OUT"] + "_seq_graph.npz", **seq(out2))
 print(json.dumps({"finite": bool(np.isfinite(rep).all()), "mean": float(rep.mean())}))
 '''
 
@@ -82,6 +98,17 @@ def test_pipelined_capture_forks(tmp_path):
         for kind in ("eager", "graph"):
             got = np.load(tmp_path / f"{name}_{kind}.npy")
             assert np.array_equal(got, ref), f"{name} {kind}: max |d| {float(np.abs(got - ref).max())}"
+    # forward(test_mode=False): init_disp and every iteration's prediction
+    ref = dict(np.load(tmp_path / "in_order_seq_eager.npz"))
+    assert sorted(ref) == ["init"] + [f"pred{i}" for i in range(4)]
+    for name in CONFIGS:
+        for kind in ("eager", "graph"):
+            got = dict(np.load(tmp_path / f"{name}_seq_{kind}.npz"))
+            assert sorted(got) == sorted(ref), (name, kind, sorted(got))
+            for k in ref:
+                assert np.isfinite(got[k]).all(), (name, kind, k)
+                assert np.array_equal(got[k], ref[k]), \
+                    f"{name} seq {kind} {k}: max |d| {float(np.abs(got[k] - ref[k]).max())}"
 
 
 @pytest.mark.gpu
@@ -100,10 +127,10 @@ def test_guard_raises_under_real_capture():
     """Forking gru08's small branch from the pipeline stream -- round 4's segfault -- raises
     CaptureForkError inside the capture instead of reaching hipStreamEndCapture (child process)."""
     code = CHILD.replace("with torch.cuda.graph(g):\n        out = model(L, R, iters=iters, test_mode=True)",
-                         "from foundationstereo_amd import update as U\n"
+                         "from foundationstereo_amd import streams, update as U\n"
                          "    real = U.SelectiveConvGRU.forward\n"
                          "    def fwd(self, *a, **k):\n"
-                         "        U._BRANCH[0] = 1\n"
+                         "        k['fork_small'] = True\n"
                          "        return real(self, *a, **k)\n"
                          "    U.SelectiveConvGRU.forward = fwd\n"
                          "    try:\n"
@@ -112,7 +139,7 @@ def test_guard_raises_under_real_capture():
                          "    except Exception as e:\n"
                          "        c, found = e, False\n"
                          "        while c is not None:\n"
-                         "            found, c = found or isinstance(c, U.CaptureForkError), c.__context__\n"
+                         "            found, c = found or isinstance(c, streams.CaptureForkError), c.__context__\n"
                          "        print(json.dumps({'raised': found})); sys.exit(0)\n"
                          "    print(json.dumps({'raised': None})); sys.exit(0)")
     env = dict(os.environ, REPO=REPO, OUT="/tmp/fsmi_guard")

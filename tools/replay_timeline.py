@@ -12,7 +12,7 @@ Prints, for iteration ``--iter`` (lookup(t) start .. lookup(t+1) start): every s
 capture stream (main / motion / branch / pipeline), start / end in us from lookup(t), duration and tag;
 the busy time per stream; and the chain that sets the iteration's length, walked back from lookup(t+1)
 through the captured graph's dependencies: each launch's own-stream predecessor plus, for every
-cross-stream wait its stream issued (logged with its capture position, update.WAIT_LOG), the waited
+cross-stream wait its stream issued (logged with its capture position, streams.WAIT_LOG), the waited
 stream's last launch before the wait; each step takes the dependency that finished last.  (Round 5's
 tool took the latest-ending launch of ANY stream at each step, which walked into the pipeline stream
 whenever one of its convs happened to end just before a main-stream launch.)  Kernels without a clock (the
@@ -35,8 +35,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import bench  # noqa: E402
-from foundationstereo_amd import _lib, ops, synth  # noqa: E402
-from foundationstereo_amd import update as fupdate  # noqa: E402
+from foundationstereo_amd import _lib, ops, streams, synth  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="cfg2")
@@ -62,11 +61,11 @@ with torch.no_grad():
         model(L, R, iters=iters, test_mode=True)
     torch.cuda.synchronize()
     ops.timer_enable(True, timeline=True)
-    fupdate.WAIT_LOG = []                    # the capture's cross-stream waits, by capture position
+    streams.WAIT_LOG = []                    # the capture's cross-stream waits, by capture position
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         model(L, R, iters=iters, test_mode=True)
-    waits, fupdate.WAIT_LOG = fupdate.WAIT_LOG, None
+    waits, streams.WAIT_LOG = streams.WAIT_LOG, None
     ops.timer_enable(False)
 for _ in range(a.replays):
     g.replay()
@@ -77,9 +76,7 @@ g.replay()
 e1.record()
 torch.cuda.synchronize()
 step_ms = e0.elapsed_time(e1)
-names = {}
-for idx, nm in ((0, "motion"), (1, "branch"), (3, "pipeline")):
-    names[fupdate._side_stream(dev, idx).cuda_stream] = nm
+names = {streams.side(dev, slot).cuda_stream: nm for slot, nm in streams.NAMES.items()}
 recs = [{"k": k, "sp": sp, "stream": names.get(sp, "main"), "s": t0, "e": t1, "tag": tag or _lib.KERNELS[k], "i": i}
         for i, (k, sp, t0, t1, tag) in enumerate(ops.timer_dump_captured())]
 # the captured graph's dependencies of each launch (capture position i): its stream's previous launch,
