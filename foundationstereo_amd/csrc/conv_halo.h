@@ -1,30 +1,34 @@
 // Halo-tiled split-precision ("3 x fp16") convolution for the refinement loop.
 //
-// conv2d_x3.hip streams an im2col view: for a 3x3 layer every pixel is staged
-// 9 times and the full weight matrix once per pixel tile (~2.8 GB of on-chip
-// traffic for one 512->512 layer at 120x160).  Here a block owns a 2D pixel
-// tile (TR rows x 32 columns of one image) and BM output channels:
+// An im2col view of a 3x3 layer stages every pixel 9 times and the full weight
+// matrix once per pixel tile (~2.8 GB of on-chip traffic for one 512->512
+// layer at 120x160).  Here a block owns a 2D pixel tile (TR rows x 32 columns
+// of one image) and BM output channels (the tiles: conv_tiles.h):
 //   * per 32-channel chunk the (TR+2) x 34 input halo is loaded ONCE, split
 //     into fp16 hi/lo and kept in LDS for all 9 taps (fragments for tap
 //     (dh,dw) are the halo rows/cols shifted by (dh,dw));
 //   * weights (pre-split, pre-packed) either go per tap through a double-
 //     buffered LDS slot whose next fill is in flight during the MFMAs
-//     (conv_halo_x3_kernel, cfg 0/1: one barrier per tap), or each wave loads
-//     its own A fragments from L2 into a double-buffered register set one tap
-//     ahead (conv_halo_wreg_kernel, cfg 2/3: LDS holds only the halo, two
-//     barriers per 32-channel chunk);
+//     (conv_halo_x3_kernel, the LDS-weight tiles: one barrier per tap), or
+//     each wave loads its own A fragments from L2 into a double-buffered
+//     register set one tap ahead (conv_halo_wreg_kernel, the register-weight
+//     tiles: LDS holds only the halo, two barriers per 32-channel chunk);
 //   * blocks are ordered cout-tile-major over an XCD-aware remap, so each XCD
 //     works on one cout slice and keeps its weights in its 4 MB L2.
 // MFMA v_mfma_f32_32x32x16_f16, three per product (lo*hi, hi*lo, hi*hi), fp32
 // accumulation.  Epilogue: bias, ReLU/GELU, alpha, gamma, residual, channel-offset store.
 //
-// Layout of the sources: this header holds the device code; each (kernel size, 2D / volume)
-// pair compiles in its own translation unit (conv_halo_k{1,3}_{2d,3d}.hip, built in parallel),
-// and conv_halo_x3.hip holds the host side (tile / split-K policy, C ABI) and the reduce pass.
+// Layout of the sources: this header holds the device code and, at its end, the launcher that
+// instantiates it from the tile table (conv_tiles.h); each (kernel size, 2D / volume) pair
+// compiles in its own translation unit (conv_halo_k{1,2,3}_{2d,3d}.hip and conv_halo_s2_3d.hip,
+// built in parallel), and conv_halo_x3.hip holds the host side (tile / split-K policy, C ABI) and
+// the reduce pass.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
+#include "conv_tiles.h"
 #include "fsmi_common.h"
 
 // activation range of the split.  Default (FSMI_HALO_RANGE 1):
@@ -133,26 +137,20 @@ struct HaloArgs {
   unsigned long long* clk;         // in-kernel launch clock (timer mode 2 / eager timing; nullptr: off)
 };
 
-// Launch conv tile configuration `cfg` (0..9) for kernel size KS, 2D maps or NCDHW volumes
-// (D3); defined in conv_halo_k<KS>_<2d|3d>.hip.  Returns FSMI_OK or an error code.
+// The launchers take a tile id of conv_tiles.h that run_halo validated and sized a.nrt / nct / npix / nco for, and
+// return FSMI_OK or an error code.  Halo tile `id` (kg 2: its K-group variant) for kernel size KS (2: the
+// transposed-conv phases) on 2D maps or NCDHW volumes (D3); defined in conv_halo_k<KS>_<2d|3d>.hip.
 template <int KS, bool D3>
-int launch_cfg(int cfg, int kg, const HaloArgs& a, hipStream_t s);
-
-// Pointwise tiles (cfg 24-26, conv_pw.hip): 1x1 2D layers with an LDS-DMA input ring.
-// pw_tile sets the tile geometry (a.nct = pixel tiles per image, npix, nco) before split-K.
-int launch_pw(int cfg, const HaloArgs& a, hipStream_t s);
+int launch_cfg(int id, int kg, const HaloArgs& a, hipStream_t s);
+// pointwise tiles (conv_pw.hip): 1x1 2D layers with an LDS-DMA input ring
+int launch_pw(int id, const HaloArgs& a, hipStream_t s);
 // stride-2 tiles, KS x KS (KS in {1, 3}) planes of the volume kernel (conv_halo_s2_3d.hip)
-int launch_s2(int ks, int cfg, const HaloArgs& a, hipStream_t s);
+int launch_s2(int ks, int id, const HaloArgs& a, hipStream_t s);
 // split-K reduce pass over a.ws (conv_halo_x3.hip)
 void split_reduce(const HaloArgs& a, hipStream_t s);
-void pw_tile(int cfg, HaloArgs& a);
-// depth-blocked (17, 1, 1) volume tile (cfg 30, conv_depth.hip)
+// depth-blocked (17, 1, 1) volume tile (kDepthTile, conv_depth.hip)
 bool depth_conv_ok(const HaloArgs& a);
 int launch_depth(HaloArgs& a, hipStream_t s);
-
-// tiles with an in-block K-group (kg = 2) instantiation: the register-weight tiles that fit two
-// waves per SIMD (<= 256 VGPRs) with 512-thread blocks
-inline bool kg2_tile(int cfg) { return cfg == 3 || cfg == 4 || cfg == 5 || cfg == 7; }
 
 }  // namespace halo
 
@@ -868,7 +866,7 @@ __device__ __forceinline__ void conv_epilogue(const HaloArgs& a, const f32x16 (&
   }
 }
 
-// ---------------------------------------------------------------- cfg 0/1: weights through LDS
+// ------------------------------------------------------- LDS-weight tiles: weights through LDS
 
 template <int KS, int BM, int TR, int WM, bool D3>
 __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
@@ -1039,7 +1037,7 @@ __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
                                            ecoef.sb, ecoef.g);
 }
 
-// ---------------------------------------------------------------- cfg 2/3: weights in registers
+// -------------------------------------------------- register-weight tiles: weights in registers
 
 // KG = 2 ("K groups"): the block runs two groups of four waves on one tile, each accumulating
 // every other (kd, channel) chunk with its own halo buffers, and sums the two halves through LDS
@@ -1453,42 +1451,41 @@ void launch_tile(const HaloArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((conv_halo_x3_kernel<KS, BM, TR, WM, D3>), dim3(grid), dim3(256), 0, s, a);
 }
 
+// Launches halo tile `id` from among the rows of conv_tiles.h that family FAM and this instantiation may take: only
+// those are instantiated, from the row's numbers -- the geometry run_halo sized the grid with.  No such row: an error.
+template <int KS, bool D3, int KG, int STR, unsigned FAM, int I = 0>
+int launch_family(int id, const HaloArgs& a, hipStream_t s) {
+  if constexpr (I == halo::kNumHaloTiles) {
+    set_error("fsmi_conv_halo: no tile %d among this kernel's (%s)", id, halo::tile_ids(FAM, D3).c_str());
+    return FSMI_ERR_ARG;
+  } else {
+    constexpr halo::HaloTile t = halo::kHaloTiles[I];
+    if constexpr ((t.fam & FAM) != 0 && !(D3 && (t.fam & halo::kTile2DOnly))) {
+      if (t.id == id) {
+        launch_tile<KS, t.BM, t.TR, t.WM, t.wreg, D3, KG, STR>(a, s);
+        return finish_launch("fsmi_conv_halo");
+      }
+    }
+    return launch_family<KS, D3, KG, STR, FAM, I + 1>(id, a, s);
+  }
+}
+
+// stride 1: KS 1 / 3 the stride-1 tiles and their K-group variants, KS 2 the transposed-conv phase tiles
+template <int KS, bool D3>
+int launch_stride1(int id, int kg, const HaloArgs& a, hipStream_t s) {
+  if constexpr (KS != 2) {
+    if (kg == 2) return launch_family<KS, D3, 2, 1, halo::kTileKG>(id, a, s);
+  }
+  FSMI_CHECK_ARG(kg == 1, "fsmi_conv_halo: 2x2 tiles have no K-group variant");
+  return launch_family<KS, D3, 1, 1, KS == 2 ? halo::kTileUp2 : halo::kTileS1>(id, a, s);
+}
+
 }  // namespace
 }  // namespace fsmi
 
-// tiles = couts x (rows x 32 px), as listed in conv_halo_x3.hip's tile_counts switch
-#define FSMI_HALO_LAUNCH_CFG(KS, D3)                                                       \
-  namespace fsmi {                                                                          \
-  namespace halo {                                                                          \
-  template <>                                                                               \
-  int launch_cfg<KS, D3>(int cfg, int kg, const HaloArgs& a, hipStream_t s) {               \
-    if (kg == 2) {                                                                          \
-      switch (cfg) {                                                                        \
-        case 3: launch_tile<KS, 128, 4, 2, true, D3, 2>(a, s); break;                       \
-        case 4: launch_tile<KS, 128, 2, 2, true, D3, 2>(a, s); break;                       \
-        case 5: launch_tile<KS, 64, 4, 1, true, D3, 2>(a, s); break;                        \
-        case 7: launch_tile<KS, 32, 4, 1, true, D3, 2>(a, s); break;                        \
-        default: set_error("fsmi_conv_halo: tile %d has no K-group variant", cfg); return FSMI_ERR_ARG; \
-      }                                                                                     \
-      return finish_launch("fsmi_conv_halo");                                               \
-    }                                                                                       \
-    switch (cfg) {                                                                          \
-      case 0: launch_tile<KS, 64, 8, 1, false, D3>(a, s); break;                            \
-      case 1: launch_tile<KS, 128, 4, 2, false, D3>(a, s); break;                           \
-      case 2: launch_tile<KS, 64, 8, 1, true, D3>(a, s); break;                             \
-      case 3: launch_tile<KS, 128, 4, 2, true, D3>(a, s); break;                            \
-      case 4: launch_tile<KS, 128, 2, 2, true, D3>(a, s); break;                            \
-      case 5: launch_tile<KS, 64, 4, 1, true, D3>(a, s); break;                             \
-      case 6: launch_tile<KS, 32, 8, 1, true, D3>(a, s); break;                             \
-      case 8: launch_tile<KS, 128, 8, 2, true, D3>(a, s); break;                            \
-      case 9: launch_tile<KS, 256, 4, 4, true, D3>(a, s); break;                            \
-      case 11:                                                                              \
-        if constexpr (!D3 && KS != 2) launch_tile<KS, 256, 5, 4, true, D3>(a, s);           \
-        else { set_error("fsmi_conv_halo: tile 11 is 2D only"); return FSMI_ERR_ARG; }      \
-        break;                                                                              \
-      default: launch_tile<KS, 32, 4, 1, true, D3>(a, s); break;                            \
-    }                                                                                       \
-    return finish_launch("fsmi_conv_halo");                                                 \
-  }                                                                                         \
-  }                                                                                         \
+// defines the launcher of one (kernel size, 2D / volume) translation unit
+#define FSMI_HALO_LAUNCH_CFG(KS, D3)                                                                    \
+  template <>                                                                                            \
+  int fsmi::halo::launch_cfg<KS, D3>(int id, int kg, const fsmi::halo::HaloArgs& a, hipStream_t s) {     \
+    return fsmi::launch_stride1<KS, D3>(id, kg, a, s);                                                   \
   }

@@ -1,28 +1,5 @@
 // 2x2x2 volume tiles of the halo conv: the eight output phases of a ConvTranspose3d(k=4, s=2, p=1)
-// (fsmi_conv3d_up2_halo_x3).  Register-weight tiles only (no K groups).
+// (fsmi_conv3d_up2_halo_x3).  The register-weight tiles of family kTileUp2 (conv_tiles.h); no K groups.
 #include "conv_halo.h"
 
-namespace fsmi {
-namespace halo {
-
-template <>
-int launch_cfg<2, true>(int cfg, int kg, const HaloArgs& a, hipStream_t s) {
-  if (kg != 1) {
-    set_error("fsmi_conv_halo: 2x2x2 tiles have no K-group variant");
-    return FSMI_ERR_ARG;
-  }
-  switch (cfg) {
-    case 2: launch_tile<2, 64, 8, 1, true, true>(a, s); break;
-    case 3: launch_tile<2, 128, 4, 2, true, true>(a, s); break;
-    case 5: launch_tile<2, 64, 4, 1, true, true>(a, s); break;
-    case 6: launch_tile<2, 32, 8, 1, true, true>(a, s); break;
-    case 7: launch_tile<2, 32, 4, 1, true, true>(a, s); break;
-    default:
-      set_error("fsmi_conv_halo: 2x2x2 tile %d (2, 3, 5, 6, 7)", cfg);
-      return FSMI_ERR_ARG;
-  }
-  return finish_launch("fsmi_conv_halo");
-}
-
-}  // namespace halo
-}  // namespace fsmi
+FSMI_HALO_LAUNCH_CFG(2, true)

@@ -60,21 +60,13 @@ __global__ __launch_bounds__(256) void conv_split_reduce4_kernel(HaloArgs a) {
   store4(a, sv, co, b, hw, a.out, a.sb, a.gamma, a.res, a.gh, a.gz, a.gatt, a.grh);
 }
 
-template <int KS, int BM, int TR, int WM>
-void tile_counts(HaloArgs& a) {
-  a.nrt = (a.H + TR - 1) / TR;
-  a.nct = (a.W + 31) / 32;
-  a.npix = a.B * a.D * a.nrt * a.nct;
-  a.nco = (a.Cout + BM - 1) / BM;
-}
-
 }  // namespace
 }  // namespace fsmi
 
 namespace fsmi {
 namespace halo {
 
-// the split-K reduce pass of a launch whose partials are in a.ws (also used by conv_lookup.hip)
+// the split-K reduce pass of a launch whose partials are in a.ws
 void split_reduce(const HaloArgs& a_in, hipStream_t s) {
   HaloArgs a = a_in;
   const long long SP = a.cstride;
@@ -102,8 +94,7 @@ unsigned long long* g_conv_ts = nullptr;
 
 namespace {
 
-// launches per tile config as launched (0..9 and 11 register / LDS tiles, 10 stride-2, 16 + c K groups,
-// 24..29 pointwise, 30 depth-blocked, 32 + c pipelined): fsmi_conv_launch_counts
+// launches per tile config as launched, indexed by halo::encode_cfg (conv_tiles.h): fsmi_conv_launch_counts
 std::atomic<long long> g_cfg_launches[64];
 
 // in-kernel clock slot of a conv launch, tagged with its shape and tile (fsmi_timer_dump_captured)
@@ -173,66 +164,60 @@ int run_halo(HaloArgs& a, const char* what, const float* const* seg_ptr, const i
     else if (KS == 3) cfg = Cout > 64 ? 3 : (a.Cin <= 64 ? 5 : 2);
     else cfg = Cout > 64 ? 4 : 5;
   }
+  using namespace halo;                            // the tile table (conv_tiles.h)
   bool d3 = D > 1 || KD > 1;
+  TileCfg tc = decode_cfg(cfg);
   if (!d3 && range_safe()) {
     // safe range mode: the volume instantiation (range mode 1: per-chunk block exponent with exact
     // accumulator rescaling) with D = KD = 1 is the same 2D conv; the pointwise tiles (mode 2 only)
-    // take the 128 x 2 x 32 register-weight tile
+    // take the 128 x 2 x 32 register-weight tile, the 2D-only 5-row tile the 256 x 4 x 32 one
     d3 = true;
-    if (cfg == 11 || cfg == 43) cfg = 9;           // the 5-row tile is 2D only
-    else if (cfg >= 24 && cfg <= 29) cfg = 4;      // (pipelined 32 + c: the plain tile c, below)
+    if (tc.kind == TileKind::halo && tc.kg == 1 && tile_in(tc.id, kTile2DOnly)) tc.id = 9;
+    else if (pw_tile(tc.id) && !tc.pipe) tc = {4, 1, false, TileKind::halo};
   }
-  if (cfg == 30) {                                 // depth-blocked (17, 1, 1) tile (conv_depth.hip)
-    FSMI_CHECK_ARG(d3 && KS == 1 && KD == 17 && a.str == 1 && !a.up, "%s: tile 30 takes (17, 1, 1) stride-1 "
-                   "volume convs", what);
+  if (tc.kind == TileKind::depth && !tc.pipe) {    // depth-blocked (17, 1, 1) tile (conv_depth.hip)
+    FSMI_CHECK_ARG(d3 && KS == 1 && KD == 17 && a.str == 1 && !a.up, "%s: tile %d takes (17, 1, 1) stride-1 "
+                   "volume convs", what, tc.id);
     a.nsplit = 1;
     a.kpc = KD * a.CinP / HKC;
     a.ws = nullptr;
     a.ts = nullptr;
     a.ovf = range_flag_device();
-    g_cfg_launches[30].fetch_add(1, std::memory_order_relaxed);
-    const int rc = halo::launch_depth(a, s);
+    g_cfg_launches[encode_cfg(tc)].fetch_add(1, std::memory_order_relaxed);
+    const int rc = launch_depth(a, s);
     if (rc != FSMI_OK) return rc;
     return finish_launch(what);
   }
-  // cfg 32 + c: register-weight tile c (2..9) of a 2D map with the pipelined staging (conv_halo.h,
+  // 32 + c: register-weight tile c of a 2D map with the pipelined staging (conv_halo.h,
   // conv_halo_pipe_kernel); the volume instantiation (safe range mode) keeps the plain tile
-  if (cfg >= 32) {
-    cfg -= 32;
-    FSMI_CHECK_ARG(((cfg >= 2 && cfg <= 9) || cfg == 11) && a.str == 1 && !a.up,
-                   "%s: pipelined tile 32 + %d (2..9, 11; stride 1)", what, cfg);
-    a.pipe = d3 ? 0 : 1;
-  }
-  const bool pw = cfg >= 24;
-  if (pw) {                                        // pointwise LDS-DMA tiles (conv_pw.hip)
-    FSMI_CHECK_ARG(cfg <= 29 && KS == 1 && !d3 && HW % 4 == 0, "%s: pointwise tile %d needs a 2D 1x1 conv with "
-                   "H*W %% 4 == 0", what, cfg);
+  FSMI_CHECK_ARG(!tc.pipe || (tc.kind == TileKind::halo && tc.kg == 1 && tile_in(tc.id, kTilePipe) && a.str == 1 &&
+                              !a.up),
+                 "%s: pipelined tile 32 + %d (%s; stride 1)", what, cfg - 32, tile_ids(kTilePipe).c_str());
+  a.pipe = tc.pipe = tc.pipe && !d3;
+  const PwTile* pw = tc.kind == TileKind::pointwise ? pw_tile(tc.id) : nullptr;
+  if (tc.kind == TileKind::pointwise) {            // LDS-DMA tiles (conv_pw.hip): BM couts x PX px of the flat plane
+    FSMI_CHECK_ARG(pw && KS == 1 && !d3 && a.str == 1 && HW % 4 == 0, "%s: pointwise tile %d needs a 2D 1x1 "
+                   "stride-1 conv with H*W %% 4 == 0", what, tc.id);
     for (int i = 0; i < nseg; ++i)
       FSMI_CHECK_ARG(reinterpret_cast<uintptr_t>(seg_ptr[i]) % 16 == 0, "%s: pointwise tile needs 16-B aligned "
                      "segments", what);
-  }
-  int kg = 1;
-  if (cfg >= 16 && !pw) {
-    kg = 2;
-    cfg -= 16;
-    FSMI_CHECK_ARG(halo::kg2_tile(cfg), "%s: tile %d has no K-group variant (16 + 3/4/5/7)", what, cfg);
-  }
-  FSMI_CHECK_ARG((cfg >= 0 && cfg <= 9) || pw || (a.str == 2 && cfg == 10) || (cfg == 11 && !d3 && KS != 2),
-                 "%s: cfg %d (0..9, 11 on 2D maps, 16 + 3/4/5/7, 24..29)", what, cfg);
-  FSMI_CHECK_ARG(a.str == 1 || (kg == 1 && (cfg == 4 || cfg == 5 || cfg == 7 || cfg == 10)),
-                 "%s: stride-2 tile %d (4, 5, 7, 10)", what, cfg);
-  if (pw) halo::pw_tile(cfg, a);
-  else switch (cfg) {                             // tile = couts x (rows x 32 px)
-    case 0: case 2: tile_counts<3, 64, 8, 1>(a); break;
-    case 1: case 3: tile_counts<3, 128, 4, 2>(a); break;
-    case 4: tile_counts<3, 128, 2, 2>(a); break;
-    case 5: tile_counts<3, 64, 4, 1>(a); break;
-    case 6: tile_counts<3, 32, 8, 1>(a); break;
-    case 8: tile_counts<3, 128, 8, 2>(a); break;
-    case 9: tile_counts<3, 256, 4, 4>(a); break;
-    case 11: tile_counts<3, 256, 5, 4>(a); break;  // 5 rows: 24 row tiles at 120 (one round at 2 cout tiles)
-    case 10: tile_counts<3, 64, 2, 2>(a); break;
-    default: tile_counts<3, 32, 4, 1>(a); break;
+    a.nrt = 1;
+    a.nct = static_cast<int>((HW + pw->PX - 1) / pw->PX);
+    a.npix = B * a.nct;
+    a.nco = (Cout + pw->BM - 1) / pw->BM;
+  } else {
+    // the family of the kernel that will launch the tile; K groups exist for the stride-1 kernels only
+    const unsigned fam = a.str == 2 ? kTileS2 : KS == 2 ? kTileUp2 : kTileS1;
+    FSMI_CHECK_ARG(tc.kg == 1 || tile_in(tc.id, kTileKG), "%s: tile %d has no K-group variant (16 + %s)", what, tc.id,
+                   tile_ids(kTileKG).c_str());
+    FSMI_CHECK_ARG(tile_in(tc.id, fam) && !(d3 && tile_in(tc.id, kTile2DOnly)) && (tc.kg == 1 || fam == kTileS1),
+                   "%s: cfg %d (this conv's tiles: %s%s)", what, tc.id, tile_ids(fam, d3).c_str(),
+                   tc.kg == 2 ? "; no K groups" : "");
+    const HaloTile& ht = *halo_tile(tc.id);        // BM couts x (TR rows x 32 px)
+    a.nrt = (H + ht.TR - 1) / ht.TR;
+    a.nct = (W + 31) / 32;
+    a.npix = B * D * a.nrt * a.nct;
+    a.nco = (Cout + ht.BM - 1) / ht.BM;
   }
   const int nck = KD * a.CinP / HKC;               // split-K runs over (kd, channel chunk) pairs
   const long long per_split = static_cast<long long>(B) * Cout * HW;
@@ -247,15 +232,15 @@ int run_halo(HaloArgs& a, const char* what, const float* const* seg_ptr, const i
     else if (per_split * nsplit > ws_floats) nsplit = static_cast<int>(max(1LL, ws_floats / per_split));
   }
   nsplit = max(1, min(nsplit, nck));
-  // in-block K groups (conv_halo.h, KG = 2; cfg 16 + c = tile c with K groups): the block's two
+  // in-block K groups (conv_halo.h, KG = 2; 16 + c = tile c with K groups): the block's two
   // wave groups split its chunks and sum through LDS -- no partials in memory, no reduce pass.
   // FSMI_HALO_KG=2 (A/B) turns every eligible split-K >= 2 into K groups + half the splits.
   static const int kg_env = [] {
     const char* e = std::getenv("FSMI_HALO_KG");
     return e ? std::atoi(e) : -1;
   }();
-  if (kg == 1 && kg_env == 2 && halo::kg2_tile(cfg) && nsplit >= 2) {   // A/B: fold a split of 2 into K groups
-    kg = 2;
+  if (tc.kg == 1 && kg_env == 2 && tile_in(tc.id, kTileKG) && nsplit >= 2) {   // A/B: fold 2 splits
+    tc.kg = 2;
     nsplit = (nsplit + 1) / 2;
   }
   a.kpc = (nck + nsplit - 1) / nsplit;
@@ -270,13 +255,18 @@ int run_halo(HaloArgs& a, const char* what, const float* const* seg_ptr, const i
     return e ? std::atoi(e) : 0;
   }();
   a.dbg = conv_dbg;
-  g_cfg_launches[(a.pipe ? 32 : 0) + (kg == 2 ? 16 : 0) + cfg].fetch_add(1, std::memory_order_relaxed);
-  a.clk = conv_clock(a, s, (a.pipe ? 32 : 0) + (kg == 2 ? 16 : 0) + cfg, KS, KD,
-                     4ll * kg * a.npix * a.nco * a.nsplit * (a.up == 2 ? 8 : a.up == 4 ? 4 : 1));
-  const int rc = a.str == 2 ? halo::launch_s2(KS, cfg, a, s) : pw ? halo::launch_pw(cfg, a, s) : KS == 2 ? (d3 ? halo::launch_cfg<2, true>(cfg, kg, a, s) : halo::launch_cfg<2, false>(cfg, kg, a, s)) : KS == 3 ? (d3 ? halo::launch_cfg<3, true>(cfg, kg, a, s) : halo::launch_cfg<3, false>(cfg, kg, a, s))
-                         : (d3 ? halo::launch_cfg<1, true>(cfg, kg, a, s) : halo::launch_cfg<1, false>(cfg, kg, a, s));
+  g_cfg_launches[encode_cfg(tc)].fetch_add(1, std::memory_order_relaxed);
+  a.clk = conv_clock(a, s, encode_cfg(tc), KS, KD,
+                     4ll * tc.kg * a.npix * a.nco * a.nsplit * (a.up == 2 ? 8 : a.up == 4 ? 4 : 1));
+  using Launcher = int (*)(int, int, const HaloArgs&, hipStream_t);   // one translation unit each: [KS - 1][d3]
+  static const Launcher stride1[3][2] = {{launch_cfg<1, false>, launch_cfg<1, true>},
+                                         {launch_cfg<2, false>, launch_cfg<2, true>},
+                                         {launch_cfg<3, false>, launch_cfg<3, true>}};
+  const int rc = a.str == 2 ? launch_s2(KS, tc.id, a, s)
+                 : pw       ? launch_pw(tc.id, a, s)
+                            : stride1[KS - 1][d3](tc.id, tc.kg, a, s);
   if (rc != FSMI_OK) return rc;
-  if (a.nsplit > 1) halo::split_reduce(a, s);
+  if (a.nsplit > 1) split_reduce(a, s);
   return finish_launch(what);
 }
 
@@ -389,70 +379,55 @@ extern "C" int fsmi_conv3d_halo_x3(const float* x, int Cin, const void* whi, con
                                 res_pre, cfg, nsplit, ws, ws_floats, stream);
 }
 
+namespace {
+
+// The transposed-conv phase launches: ConvTranspose(k=4, s=2, p=1) as `phases` 2x2(x2) stride-1 convs
+// over the input in one launch -- 8 on a volume, 4 on a 2D map (D = 1).
+int run_up2(const char* what, int phases, const float* x, int Cin, const void* const* whi, const void* const* wlo,
+            const float* const* scale_bias, float* out, int B, int Cout, int D, int H, int W, int act, int cfg,
+            void* stream) {
+  FSMI_CHECK_ARG(x && out && whi && wlo && scale_bias && Cin > 0, "%s: null pointer / channels", what);
+  FSMI_CHECK_ARG(act == 0 || act == 1 || act == 6, "%s: act %d (0, 1, 6)", what, act);
+  FSMI_CHECK_ARG(halo::tile_in(cfg, halo::kTileUp2), "%s: tile %d (%s)", what, cfg,
+                 halo::tile_ids(halo::kTileUp2).c_str());
+  HaloArgs a{};
+  for (int p = 0; p < 8; ++p) {
+    const int q = p < phases ? p : 0;               // four phases: 4..7 are never selected; keep the array defined
+    FSMI_CHECK_ARG(whi[q] && wlo[q] && scale_bias[q], "%s: null phase %d", what, q);
+    FSMI_CHECK_ARG(reinterpret_cast<uintptr_t>(scale_bias[q]) % 8 == 0, "%s: scale_bias align", what);
+    a.whi8[p] = static_cast<const _Float16*>(whi[q]);
+    a.wlo8[p] = static_cast<const _Float16*>(wlo[q]);
+    a.sb8[p] = reinterpret_cast<const float2*>(scale_bias[q]);
+  }
+  a.act = act;
+  a.alpha = 1.f;
+  a.up = phases == 8 ? 2 : 4;                       // all phases in one launch
+  a.ocstride = static_cast<long long>(phases) * D * H * W;
+  const float* seg[1] = {x};
+  const int ch[1] = {Cin}, tot[1] = {Cin};
+  // out_ctot = phases * Cout: run_halo's batch stride (out_ctot x the input volume) is then the
+  // upsampled (Cout, 2D, 2H, 2W) / (Cout, 2H, 2W) output's
+  return run_halo(a, what, seg, ch, tot, 1, whi[0], wlo[0], scale_bias[0], out, phases * Cout, 0, B, Cout, 2, H, W,
+                  cfg, 1, nullptr, 0, stream, D, phases == 8 ? 2 : 1);
+}
+
+}  // namespace
+
 extern "C" int fsmi_conv3d_up2_halo_x3(const float* x, int Cin, const void* const* whi, const void* const* wlo,
                                        const float* const* scale_bias, float* out, int B, int Cout, int D, int H,
                                        int W, int act, int cfg, void* stream) {
-  FSMI_CHECK_ARG(x && out && whi && wlo && scale_bias && Cin > 0, "fsmi_conv3d_up2_halo_x3: null pointer / channels");
-  FSMI_CHECK_ARG(act == 0 || act == 1 || act == 6, "fsmi_conv3d_up2_halo_x3: act %d (0, 1, 6)", act);
   // tools/up3d_bench.py at cfg2 (one launch, 8 phases): 32-cout x 4-row tiles for 28 and 112 couts,
   // 64 x 8 for 56 (conv1_up 296 us, conv2_up 139 us, conv3_up 64 us vs 711 / 249 / 97 us for
   // MIOpen / CK + BatchNorm + LeakyReLU)
   if (cfg < 0) cfg = (Cout > 32 && Cout <= 64) ? 2 : 7;
-  FSMI_CHECK_ARG(cfg == 2 || cfg == 3 || cfg == 5 || cfg == 6 || cfg == 7,
-                 "fsmi_conv3d_up2_halo_x3: tile %d (2, 3, 5, 6, 7)", cfg);
-  const long long V = static_cast<long long>(D) * H * W;
-  HaloArgs a{};
-  for (int p = 0; p < 8; ++p) {
-    FSMI_CHECK_ARG(whi[p] && wlo[p] && scale_bias[p], "fsmi_conv3d_up2_halo_x3: null phase %d", p);
-    FSMI_CHECK_ARG(reinterpret_cast<uintptr_t>(scale_bias[p]) % 8 == 0, "fsmi_conv3d_up2_halo_x3: scale_bias align");
-    a.whi8[p] = static_cast<const _Float16*>(whi[p]);
-    a.wlo8[p] = static_cast<const _Float16*>(wlo[p]);
-    a.sb8[p] = reinterpret_cast<const float2*>(scale_bias[p]);
-  }
-  a.act = act;
-  a.alpha = 1.f;
-  a.up = 2;                                       // all eight phases in one launch
-  a.ocstride = 8 * V;
-  const float* seg[1] = {x};
-  const int ch[1] = {Cin}, tot[1] = {Cin};
-  // out_ctot = 8 * Cout: run_halo's batch stride (out_ctot x the input volume) is then the
-  // (Cout, 2D, 2H, 2W) output's
-  const int rc = run_halo(a, "fsmi_conv3d_up2_halo_x3", seg, ch, tot, 1, whi[0], wlo[0], scale_bias[0], out,
-                          8 * Cout, 0, B, Cout, 2, H, W, cfg, 1, nullptr, 0, stream, D, 2);
-  if (rc != FSMI_OK) return rc;
-  return FSMI_OK;
+  return run_up2("fsmi_conv3d_up2_halo_x3", 8, x, Cin, whi, wlo, scale_bias, out, B, Cout, D, H, W, act, cfg, stream);
 }
 
 extern "C" int fsmi_conv2d_up2_halo_x3(const float* x, int Cin, const void* const* whi, const void* const* wlo,
                                        const float* const* scale_bias, float* out, int B, int Cout, int H, int W,
                                        int act, int cfg, void* stream) {
-  FSMI_CHECK_ARG(x && out && whi && wlo && scale_bias && Cin > 0, "fsmi_conv2d_up2_halo_x3: null pointer / channels");
-  FSMI_CHECK_ARG(act == 0 || act == 1 || act == 6, "fsmi_conv2d_up2_halo_x3: act %d (0, 1, 6)", act);
   // ConvTranspose2d(k=4, s=2, p=1) as four 2x2 stride-1 phase convs over the input (the 2D analogue of
   // fsmi_conv3d_up2_halo_x3); 32-cout x 4-row tiles unless told otherwise (the spx layers: 32 and 9 couts)
   if (cfg < 0) cfg = Cout > 64 ? 3 : (Cout > 32 ? 5 : 7);
-  FSMI_CHECK_ARG(cfg == 2 || cfg == 3 || cfg == 5 || cfg == 6 || cfg == 7,
-                 "fsmi_conv2d_up2_halo_x3: tile %d (2, 3, 5, 6, 7)", cfg);
-  HaloArgs a{};
-  for (int p = 0; p < 4; ++p) {
-    FSMI_CHECK_ARG(whi[p] && wlo[p] && scale_bias[p], "fsmi_conv2d_up2_halo_x3: null phase %d", p);
-    FSMI_CHECK_ARG(reinterpret_cast<uintptr_t>(scale_bias[p]) % 8 == 0, "fsmi_conv2d_up2_halo_x3: scale_bias align");
-    a.whi8[p] = static_cast<const _Float16*>(whi[p]);
-    a.wlo8[p] = static_cast<const _Float16*>(wlo[p]);
-    a.sb8[p] = reinterpret_cast<const float2*>(scale_bias[p]);
-  }
-  for (int p = 4; p < 8; ++p) {       // never selected (four phases); keep the array defined
-    a.whi8[p] = a.whi8[0];
-    a.wlo8[p] = a.wlo8[0];
-    a.sb8[p] = a.sb8[0];
-  }
-  a.act = act;
-  a.alpha = 1.f;
-  a.up = 4;                                       // the four phases of a 2D map in one launch
-  a.ocstride = 4ll * H * W;
-  const float* seg[1] = {x};
-  const int ch[1] = {Cin}, tot[1] = {Cin};
-  // out_ctot = 4 * Cout: run_halo's batch stride (out_ctot x the input plane) is the (Cout, 2H, 2W) output's
-  return run_halo(a, "fsmi_conv2d_up2_halo_x3", seg, ch, tot, 1, whi[0], wlo[0], scale_bias[0], out, 4 * Cout, 0, B,
-                  Cout, 2, H, W, cfg, 1, nullptr, 0, stream, 1, 1);
+  return run_up2("fsmi_conv2d_up2_halo_x3", 4, x, Cin, whi, wlo, scale_bias, out, B, Cout, 1, H, W, act, cfg, stream);
 }

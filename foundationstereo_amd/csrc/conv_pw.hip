@@ -1,4 +1,5 @@
-// Pointwise (1x1) split-precision convolution with a multi-stage LDS-DMA input ring (cfg 24-26).
+// Pointwise (1x1) split-precision convolution with a multi-stage LDS-DMA input ring (the tiles of
+// kPwTiles, conv_tiles.h).
 //
 // A 1x1 layer gives the halo kernel one tap of MFMA work per 32-channel chunk, too little to
 // cover the chunk's global round trip with one chunk of prefetch: the loop's 1x1 layers ran at
@@ -15,7 +16,7 @@
 //   * range mode 2 (conv_halo.h): the block exponent is fixed from the first chunk with 8 bits of
 //     headroom; a value beyond fp16's range sets the range flag;
 //   * same split-K partials / reduce pass and the same epilogues (store_frag) as the halo tiles.
-// Entry: run_halo (conv_halo_x3.hip) with cfg 24-26; KS = 1, 2D, H*W % 4 == 0, 16-B aligned segments.
+// Entry: run_halo (conv_halo_x3.hip) with a pointwise cfg; KS = 1, 2D, H*W % 4 == 0, 16-B aligned segments.
 #include "conv_halo.h"
 
 #ifndef FSMI_PW_TWOBAR
@@ -324,35 +325,23 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
 
 namespace halo {
 
-// cfg 24: 128 couts x 128 px (2 x 2 fragments per wave), 3-deep ring; 25: 128 x 64 (2 x 1), 4 deep;
-// 26: 64 x 128 (2 x 1, waves along the pixels), 3 deep.  The block-split (COOP) tiles: 27: 256 x 64
-// (2 x 2 per wave, waves along the couts), 4 deep; 28: 128 x 64 (2 x 1), 4 deep; 29: 128 x 128
-// (2 x 2), 3 deep.  Deeper rings (6 / 8 chunks, 64-96 KB of
-// LDS) measured 5-40 % slower on every cfg2 1x1 shape (tools/pw_bench.py), so the chunk round
-// trip is not what bounds these layers.  Tile geometry (a.nct = pixel tiles per image, a.npix, a.nco) is set by
-// the caller (pw_tile).
-int launch_pw(int cfg, const HaloArgs& a, hipStream_t s) {
-  const unsigned grid = static_cast<unsigned>(a.npix) * a.nco * a.nsplit;
-  switch (cfg) {
-    case 24: hipLaunchKernelGGL((conv_pw_kernel<128, 128, 2, 3>), dim3(grid), dim3(256), 0, s, a); break;
-    case 25: hipLaunchKernelGGL((conv_pw_kernel<128, 64, 2, 4>), dim3(grid), dim3(256), 0, s, a); break;
-    case 26: hipLaunchKernelGGL((conv_pw_kernel<64, 128, 1, 3>), dim3(grid), dim3(256), 0, s, a); break;
-    case 27: hipLaunchKernelGGL((conv_pw_kernel<256, 64, 4, 4, true>), dim3(grid), dim3(256), 0, s, a); break;
-    case 28: hipLaunchKernelGGL((conv_pw_kernel<128, 64, 2, 4, true>), dim3(grid), dim3(256), 0, s, a); break;
-    case 29: hipLaunchKernelGGL((conv_pw_kernel<128, 128, 2, 3, true>), dim3(grid), dim3(256), 0, s, a); break;
-    default: set_error("fsmi_conv_halo: pointwise tile %d (24..29)", cfg); return FSMI_ERR_ARG;
+// one instantiation per row of kPwTiles (conv_tiles.h); the geometry (a.nct = pixel tiles per image,
+// a.npix, a.nco) is set by the caller from the same row
+template <int I = 0>
+static int launch_pw_row(int id, const HaloArgs& a, hipStream_t s) {
+  if constexpr (I == kNumPwTiles) {
+    set_error("fsmi_conv_halo: no pointwise tile %d", id);
+    return FSMI_ERR_ARG;
+  } else {
+    constexpr PwTile t = kPwTiles[I];
+    if (t.id != id) return launch_pw_row<I + 1>(id, a, s);
+    const unsigned grid = static_cast<unsigned>(a.npix) * a.nco * a.nsplit;
+    hipLaunchKernelGGL((conv_pw_kernel<t.BM, t.PX, t.WM, t.NS, t.coop>), dim3(grid), dim3(256), 0, s, a);
+    return finish_launch("fsmi_conv_halo");
   }
-  return finish_launch("fsmi_conv_halo");
 }
 
-void pw_tile(int cfg, HaloArgs& a) {
-  const int BM = cfg == 26 ? 64 : cfg == 27 ? 256 : 128, PX = (cfg == 25 || cfg == 27 || cfg == 28) ? 64 : 128;
-  const long long HW = a.cstride;
-  a.nrt = 1;
-  a.nct = static_cast<int>((HW + PX - 1) / PX);
-  a.npix = a.B * a.nct;
-  a.nco = (a.Cout + BM - 1) / BM;
-}
+int launch_pw(int id, const HaloArgs& a, hipStream_t s) { return launch_pw_row(id, a, s); }
 
 }  // namespace halo
 }  // namespace fsmi

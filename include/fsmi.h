@@ -168,14 +168,15 @@ int fsmi_conv3d_direct(const float* x, const float* w, const float* bias, float*
  * kernel (conv_halo.h, chunk_exp), so neither overflows fp16 nor loses its low
  * half to fp16 subnormals.  A block stages a (rows+2)x34 input halo once per
  * 32-channel chunk and runs all taps from LDS.  Inner segments must hold a
- * multiple of 8 channels.  cfg 0: 64 couts x 8x32 px, 1: 128 couts x 4x32 px
- * (weights staged per tap through LDS); 2 / 3: the same tiles with each wave's
- * weight fragments loaded into registers one tap ahead; 4: 128 couts x 2x32 px,
- * 5: 64 couts x 4x32 px (registers, one pixel fragment per wave: 3 waves/SIMD);
- * 8: 128 couts x 8x32 px, 9: 256 couts x 4x32 px (registers, 2x4 fragments per wave);
- * 16 + c (c in 3, 4, 5, 7): tile c with two K groups -- 512-thread blocks whose two wave
- * groups take alternate 32-channel chunks and sum through LDS (split-K inside the block);
- * -1: measured default.
+ * multiple of 8 channels.  cfg names the tile, couts x (rows x 32 px), of the table csrc/conv_tiles.h:
+ *   c (0..11): halo tile c (0 / 1 stage weights per tap through LDS, the others keep each wave's
+ *     weight fragments in registers, loaded one tap ahead; 10 is stride 2 only, 11 2D only);
+ *   16 + c: tile c with two K groups -- 512-thread blocks whose two wave groups take
+ *     alternate 32-channel chunks and sum through LDS (split-K inside the block);
+ *   24..29: the pointwise LDS-DMA tiles (2D 1x1 layers, H*W % 4 == 0, 16-B aligned segments);
+ *   30: the depth-blocked tile ((17,1,1) volume convs);
+ *   32 + c: register-weight tile c with pipelined staging (2D maps; a volume runs tile c);
+ *   -1: measured default.  A cfg the table does not give the conv is FSMI_ERR_ARG.
  * nsplit: split-K over 32-channel chunks (<0: auto, sized to fill the chip);
  * partial sums go to ws (nsplit*B*Cout*H*W floats, ws_floats available) and
  * a second kernel sums them in split order (deterministic) and applies the
@@ -183,9 +184,8 @@ int fsmi_conv3d_direct(const float* x, const float* w, const float* bias, float*
  * (A last-arriving-block fixup inside the conv kernel was measured 4x slower:
  * the agent-scope fences it needs flush and invalidate the per-XCD L2.) */
 /* Launches of the halo / pointwise / depth conv tiles since the last reset, per tile config as
- * launched: counts[c] for c < n (n <= 64): 0..9 and 11 register / LDS tiles, 10 stride-2 tiles,
- * 16 + c K-group tiles, 24..29 pointwise tiles, 30 the depth-blocked (17,1,1) tile, 32 + c the
- * pipelined variant of tile c.  reset != 0 zeroes them after the read.  (Which tile the tuning table
+ * launched: counts[c] for c < n (n <= 64), c in the cfg encoding of fsmi_conv2d_halo_x3 below
+ * (csrc/conv_tiles.h).  reset != 0 zeroes them after the read.  (Which tile the tuning table
  * or the policy picked for a layer, checked by tests.) */
 int fsmi_conv_launch_counts(long long* counts, int n, int reset);
 
@@ -223,7 +223,7 @@ int fsmi_conv2d_halo_x3_gate(const float* const* seg_ptr, const int* seg_ch, con
  * fsmi_conv2d_halo_x3 with taps = (kd, kh, kw), kd major; bias = folded conv bias +
  * BatchNorm shift.  out = act(conv + bias) + res, or with res_pre
  * act(conv + bias + res); act 0 none, 1 ReLU, 6 LeakyReLU(0.01).
- * cfg as fsmi_conv2d_halo_x3 plus 6: 32 couts x 8x32 px, 7: 32 x 4x32. */
+ * cfg as fsmi_conv2d_halo_x3 (no 2D-only or pointwise tile on a volume). */
 int fsmi_conv3d_halo_x3(const float* x, int Cin, const void* whi, const void* wlo, const float* scale_bias,
                         const float* res, float* out, int B, int Cout, int D, int H, int W, int KD, int KS,
                         int act, int res_pre, int cfg, int nsplit, float* ws, long long ws_floats, void* stream);
@@ -234,7 +234,7 @@ int fsmi_conv3d_halo_x3(const float* x, int Cin, const void* whi, const void* wl
  *     (core/foundation_stereo.py:50-58), and with D = KD = 1 the context net's 3x3 s2 p1 convs and
  *     1x1 s2 projections (core/extractor.py:20-80): KS, KD in {1, 3} with padding KS/2, KD/2;
  *     D, H, W are the INPUT's, out / res are (B, Cout, (D-1)/2+1, (H-1)/2+1, (W-1)/2+1); cfg -1 or
- *     the stride-2 tiles 4 (128 couts x 2x32 px), 5 (64 x 4x32), 7 (32 x 4x32), 10 (64 x 2x32).
+ *     one of the table's stride-2 tiles (4, 5, 7, 10).
  *   res_pre needs a volume (D or KD > 1) or stride 2 (FSMI_ERR_ARG otherwise).
  *   fatt: FeatureAtt (core/submodule.py:438-454) folded into the epilogue -- the final value of
  *     output channel co at (d, h, w) is multiplied by sigmoid(fatt[b, co, h, w]); fatt is the
@@ -256,8 +256,8 @@ int fsmi_conv3d_halo_x3_ex(const float* x, int Cin, const void* whi, const void*
  * p = 4*pd + 2*ph + pw (voxels (2d+pd, 2h+ph, 2w+pw)) is a 2x2x2 stride-1 conv over x:
  * whi[p] / wlo[p] packed as fsmi_conv3d_halo_x3's weights (KD = KS = 2, taps at input offsets
  * {-1, 0} for phase 0 and {0, +1} for phase 1 of each dimension; ops.pack_deconv_phases),
- * scale_bias[p] its (2^-wexp, bias) pairs.  act 0 none / 1 ReLU / 6 LeakyReLU(0.01); cfg tile
- * (2, 3, 5, 6, 7) or -1. */
+ * scale_bias[p] its (2^-wexp, bias) pairs.  act 0 none / 1 ReLU / 6 LeakyReLU(0.01); cfg one of
+ * the table's transposed-conv phase tiles (2, 3, 5, 6, 7) or -1. */
 int fsmi_conv3d_up2_halo_x3(const float* x, int Cin, const void* const* whi, const void* const* wlo,
                             const float* const* scale_bias, float* out, int B, int Cout, int D, int H, int W,
                             int act, int cfg, void* stream);

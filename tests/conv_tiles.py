@@ -1,5 +1,7 @@
-"""Tile ids (``cfg``) a conv may take, read off ``run_halo`` in csrc/conv_halo_x3.hip and ``launch_cfg`` in
-csrc/conv_halo.h.
+"""Tile ids (``cfg``) a conv may take: the tests' own statement, written by hand, of what the tile table
+csrc/conv_tiles.h (rows, family masks, ``decode_cfg``) and ``run_halo`` in csrc/conv_halo_x3.hip accept.
+tests/test_tiles_host.py probes the C entry points against these lists on the CPU; a tile added to or retired
+from the table is added or retired here by hand as well.
 
 2D, stride 1: tile c (0..9, 11) = couts x (rows x 32 px); 16 + c the K-group variant of c in {3, 4, 5, 7};
 32 + c the pipelined-staging variant of c in {2..9, 11}; 24..29 the pointwise LDS-DMA tiles (conv_pw.hip).

@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 import oracle
 from foundationstereo_amd import synth
-from tests.conv_tiles import HALO_2D
+from tests.conv_tiles import HALO_2D, S2_3D, UP2
 from tests.helpers import load_golden, model_keys, oracle_params, t
 
 pytestmark = pytest.mark.gpu
@@ -319,6 +319,58 @@ def test_conv3d_s2_vs_torch(ops_mod, cin, cout, D, H, W, B, cfg, nsplit):
     assert out.shape == ref.shape
     close(out, ref, atol=2e-5, rtol=1e-5)
     assert not ops_mod.range_overflowed(reset=True)
+
+
+def test_s2_and_up2_tiles_run_as_asked(ops_mod):
+    """Every stride-2 and transposed-conv phase tile id (tests/conv_tiles.py) launches exactly one conv, counted
+    under that id, and matches fp64 torch (2e-5 abs + 1e-5 rel, as the tests above); every other halo tile id is
+    refused with nothing launched.  40 -> 37 channels (two channel chunks, a ragged cout fragment) on maps with
+    ragged row and column tiles: stride-2 input (5, 9, 37), phase inputs (2, 5, 33) and (5, 33), batch 2."""
+    from foundationstereo_amd import _lib
+    ops, B, cin, cout = ops_mod, 2, 40, 37
+    gen = torch.Generator().manual_seed(4037)
+    sc = torch.rand(cout, generator=gen) + 0.5
+    bias = torch.randn(cout, generator=gen) * 0.1
+
+    def col(v, nd):
+        return v.double().view(1, -1, *([1] * nd))
+
+    x = torch.randn(B, cin, 5, 9, 37, generator=gen)
+    w = torch.randn(cout, cin, 3, 3, 3, generator=gen) * 0.05
+    pk = ops.PackedConv(g(w), mode="halo")
+    ref_s2 = F.leaky_relu(F.conv3d(x.double(), w.double(), bias.double(), stride=2, padding=1), 0.01)
+
+    x3 = torch.randn(B, cin, 2, 5, 33, generator=gen)
+    w3 = torch.randn(cin, cout, 4, 4, 4, generator=gen) * 0.05
+    pk3 = ops.pack_deconv_phases(g(w3), g(sc))
+    ref_up3 = F.leaky_relu(F.conv_transpose3d(x3.double(), w3.double(), stride=2, padding=1) * col(sc, 3)
+                           + col(bias, 3), 0.01)
+
+    x2 = torch.randn(B, cin, 5, 33, generator=gen)
+    w2 = torch.randn(cin, cout, 4, 4, generator=gen) * 0.05
+    pk2 = ops.pack_deconv2d_phases(g(w2), g(sc))
+    ref_up2 = F.leaky_relu(F.conv_transpose2d(x2.double(), w2.double(), stride=2, padding=1) * col(sc, 2)
+                           + col(bias, 2), 0.01)
+
+    xs, x3, x2, b = g(x), g(x3), g(x2), g(bias)
+    cases = [("s2", S2_3D, ref_s2, lambda c: ops.conv3d(xs, pk, bias=b, act="leaky", stride=2, cfg=c, nsplit=1)),
+             ("up2 3d", UP2, ref_up3, lambda c: ops.conv3d_up2(x3, pk3, bias=b, act="leaky", cfg=c)),
+             ("up2 2d", UP2, ref_up2, lambda c: ops.conv2d_up2(x2, pk2, bias=b, act="leaky", cfg=c))]
+    for name, ids, ref, run in cases:
+        for cfg in range(12):
+            ops.conv_launch_counts(reset=True)
+            if cfg not in ids:
+                with pytest.raises(_lib.FsmiError):
+                    run(cfg)
+                assert sum(ops.conv_launch_counts()) == 0, f"{name}: refused tile {cfg} launched a conv"
+                continue
+            out = run(cfg)
+            counts = ops.conv_launch_counts(reset=True)
+            assert sum(counts) == 1 and counts[cfg] == 1, \
+                f"{name} tile {cfg}: launches {[(i, n) for i, n in enumerate(counts) if n]}"
+            assert out.shape == ref.shape
+            close(out, ref, atol=2e-5, rtol=1e-5)
+    assert not ops.range_overflowed(reset=True)
 
 
 @pytest.mark.parametrize("k,cin,cout,H,W,res", [(3, 64, 96, 120, 160, False), (1, 64, 96, 120, 160, True),
