@@ -10,7 +10,9 @@ demo end to end (``python -m foundationstereo_amd.demo``), and ``metrics``:
 EPE / RMSE / bad-pixel rates / D1 of a disparity against a ground truth
 (``python -m foundationstereo_amd.evaluate``), and ``losses``: every
 refinement iteration scored in one pass, the reference's sequence loss and
-the convergence curve (``evaluate --per_iter``).  See DESIGN.md.
+the convergence curve (``evaluate --per_iter``), and ``visibility``: an
+occlusion z-buffer and the left-right check, one class per pixel
+(``demo --occlusion_check``, ``evaluate --noc``).  See DESIGN.md.
 """
 import os as _os
 

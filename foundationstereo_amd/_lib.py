@@ -72,6 +72,7 @@ SIGNATURES = {
     "fsmi_disp_to_xyz": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _I, _P],
     "fsmi_cloud_cell_keys": [_P, _P, _P, _I, _F, _P],
     "fsmi_radius_count": [_P, _P, _P, _P, _I, _F, _I, _P],
+    "fsmi_disp_visibility": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P],
     "fsmi_frames_ingest": [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _I, _I, _I, _P],
     "fsmi_disp_minmax": [_P, _P, _I, _I, _I, _F, _P],
     "fsmi_disp_colorize": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],

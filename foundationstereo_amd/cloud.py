@@ -54,29 +54,37 @@ def _camera(K, scale: float):
 
 
 def disparity_to_xyz(disp: Tensor, K, baseline: float, *, scale: float = 1.0, camera_type: str = "pinhole",
-                     remove_invisible: bool = True, zmin: float = 0.1, z_far: float = 10.0
-                     ) -> Tuple[Tensor, Tensor, Tensor]:
+                     remove_invisible: bool = True, zmin: float = 0.1, z_far: float = 10.0,
+                     keep: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
     """``(xyz_map (B,H,W,3), depth (B,H,W), valid (B,H,W) bool)`` of a disparity map on a HIP device.
 
     ``K`` is any 3x3 array-like on the host (ignored by ``camera_type="panorama"``) and ``scale`` the
-    factor the images were resized by before the forward.  No host synchronisation."""
+    factor the images were resized by before the forward.  ``keep``, a bool (B,H,W) mask on the device
+    of ``disp`` such as ``visibility.classify(disp).visible``, is ANDed into ``valid`` after the kernel;
+    ``xyz_map`` and ``depth`` stay as they are.  No host synchronisation."""
     fx, fy, cx, cy = _camera(K, scale)
-    return ops.disp_to_xyz(_as_bhw(disp), fx, fy, cx, cy, baseline, zmin=zmin, z_far=z_far,
-                           remove_invisible=remove_invisible, camera_type=camera_type)
+    xyz, depth, valid = ops.disp_to_xyz(_as_bhw(disp), fx, fy, cx, cy, baseline, zmin=zmin, z_far=z_far,
+                                        remove_invisible=remove_invisible, camera_type=camera_type)
+    if keep is not None:
+        if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.shape != valid.shape \
+                or keep.device != valid.device:
+            raise ValueError(f"keep must be a bool mask {tuple(valid.shape)} on {valid.device}")
+        valid = valid & keep
+    return xyz, depth, valid
 
 
 def disparity_to_cloud(disp: Tensor, K, baseline: float, image: Optional[Tensor] = None, *, denoise: bool = True,
                        nb_points: int = 30, radius: float = 0.03, scale: float = 1.0,
                        camera_type: str = "pinhole", remove_invisible: bool = True, zmin: float = 0.1,
-                       z_far: float = 10.0) -> List[Cloud]:
+                       z_far: float = 10.0, keep: Optional[Tensor] = None) -> List[Cloud]:
     """The demo's cloud (scripts/run_demo.py:173-275) per batch element.
 
     ``image``: (B,3,H,W), (B,H,W,3), (3,H,W) or (H,W,3) on the device of ``disp``; its values at the
     kept pixels become ``colors``.  ``denoise`` applies the radius outlier removal to the valid
-    points.  Everything queues on the current stream; the compaction ``xyz_map[inliers]`` is the one
+    points; ``keep`` (``disparity_to_xyz``) takes pixels out of ``valid`` before it.  Everything queues on the current stream; the compaction ``xyz_map[inliers]`` is the one
     step that synchronises."""
     xyz, depth, valid = disparity_to_xyz(disp, K, baseline, scale=scale, camera_type=camera_type,
-                                         remove_invisible=remove_invisible, zmin=zmin, z_far=z_far)
+                                         remove_invisible=remove_invisible, zmin=zmin, z_far=z_far, keep=keep)
     B, H, W = depth.shape
     if image is not None:
         if image.dim() == 3:

@@ -13,6 +13,7 @@
 //   context_upsample    core/submodule.py:456-468      softmax_context_upsample core/foundation_stereo.py:187-189
 //   disp_to_xyz         scripts/run_demo.py:173-251, Utils.py:56-75
 //   radius_outlier_mask scripts/run_demo.py:270-273 (Open3D remove_radius_outlier)
+//   disp_visibility     no reference counterpart (occlusion z-buffer, left-right check; include/fsmi.h)
 //   frames_ingest       scripts/run_demo.py:131-159   vis_disparity     Utils.py:108-133
 //   disp_metrics        train/utils.py:88-141, train/losses.py:326-339   gt_decode  Utils.py:137-140
 //   seq_metrics         train/losses.py:20-187, :379-498
@@ -263,6 +264,33 @@ Tensor radius_outlier_mask(const Tensor& points_, const c10::optional<Tensor>& v
   return keep.view(at::kBool);
 }
 
+// ops.disp_visibility: (classes, counts, error); error has no element when want_error is false
+std::tuple<Tensor, Tensor, Tensor> disp_visibility(const Tensor& disp_, const c10::optional<Tensor>& disp_right_,
+                                                   double occlusion_tol, double lr_thresh, bool occlusion,
+                                                   bool want_error) {
+  const c10::DeviceGuard guard(disp_.device());
+  check_dev("disp_visibility", disp_);
+  TORCH_CHECK(disp_.dim() == 3, "disp_visibility: disp must be (B,H,W)");
+  Tensor disp = dense(disp_), right;
+  if (disp_right_.has_value() && disp_right_->defined()) {
+    check_dev("disp_visibility", *disp_right_);
+    TORCH_CHECK(disp_right_->sizes() == disp.sizes() && disp_right_->device() == disp.device(),
+                "disp_visibility: disp_right must have the shape and device of disp");
+    right = dense(*disp_right_);
+  }
+  TORCH_CHECK(!want_error || right.defined(), "disp_visibility: want_error needs disp_right");
+  const int64_t B = disp.size(0), H = disp.size(1), W = disp.size(2);
+  Tensor classes = at::empty({B, H, W}, disp.options().dtype(at::kByte));
+  Tensor counts = at::empty({B, FSMI_VIS_NCLASS}, disp.options().dtype(at::kLong));
+  Tensor error = want_error ? at::empty({B, H, W}, disp.options()) : at::empty({0}, disp.options());
+  ok(fsmi_disp_visibility(cp(disp), right.defined() ? cp(right) : nullptr, classes.data_ptr<uint8_t>(),
+                          want_error ? mp(error) : nullptr, reinterpret_cast<long long*>(counts.data_ptr<int64_t>()),
+                          (int)B, (int)H, (int)W, (float)occlusion_tol, (float)lr_thresh, occlusion ? 1 : 0,
+                          stream_of(disp)),
+     "disp_visibility");
+  return {classes, counts, error};
+}
+
 void check_u8(const char* name, const Tensor& t) {
   TORCH_CHECK(t.is_cuda(), name, ": fsmi ops run on ROCm (HIP) device tensors only; got ", t.device());
   TORCH_CHECK(t.scalar_type() == at::kByte, name, ": expected uint8, got ", t.scalar_type());
@@ -476,6 +504,9 @@ TORCH_LIBRARY(fsmi, m) {
   m.def("disp_to_xyz(Tensor disp, float fx, float fy, float cx, float cy, float baseline, float zmin=0.1, "
         "float z_far=10.0, bool remove_invisible=True, int camera_type=0) -> (Tensor, Tensor, Tensor)");
   m.def("radius_outlier_mask(Tensor points, Tensor? valid=None, int nb_points=30, float radius=0.03) -> Tensor");
+  // visibility classes (include/fsmi.h): (classes, counts, error); error is empty unless want_error
+  m.def("disp_visibility(Tensor disp, Tensor? disp_right, float occlusion_tol, float lr_thresh, bool occlusion, "
+        "bool want_error) -> (Tensor, Tensor, Tensor)");
   // around the forward (scripts/run_demo.py:131-170): (batch, image_u8) and (picture, minmax)
   m.def("frames_ingest(Tensor left, Tensor right, float scale=1.0, int divis_by=32) -> (Tensor, Tensor)");
   // invalid_thres=None is +inf, the reference's default (the schema grammar has no literal for it)
@@ -505,6 +536,7 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("softmax_context_upsample", softmax_context_upsample);
   m.impl("disp_to_xyz", disp_to_xyz);
   m.impl("radius_outlier_mask", radius_outlier_mask);
+  m.impl("disp_visibility", disp_visibility);
   m.impl("frames_ingest", frames_ingest);
   m.impl("vis_disparity", vis_disparity);
   m.impl("disp_metrics", disp_metrics);

@@ -8,7 +8,9 @@ Frames in (``frames.ingest``), forward, picture (``frames.vis_disparity``), dept
 ``vis.png``, ``depth_meter.npy`` (pinhole only), ``cloud.ply`` and ``cloud_denoise.ply`` into
 ``--out_dir`` next to copies of the inputs, and prints one JSON line.  The flags carry the reference's
 names and defaults (run_demo.py:45-80); ``--out_dir`` is honoured (the reference replaces it with a
-timestamped folder) and no viewer window opens.  ``--synthetic`` runs without a checkpoint on the
+timestamped folder) and no viewer window opens.  ``--occlusion_check 1`` and ``--lr_check 1`` (not in the
+reference; ``visibility``) draw the picture and build the clouds from the VISIBLE pixels only, write
+``visibility.png`` and add the five class counts to the JSON line.  ``--synthetic`` runs without a checkpoint on the
 hash-initialised model the tests use.
 """
 from __future__ import annotations
@@ -24,14 +26,27 @@ import torch
 
 from . import cloud, frames
 
+# visibility.png: one grey level per class, in code order (visible, invalid, out_of_view, occluded, mismatch)
+VISIBILITY_GREY = (255, 0, 64, 128, 192)
+
 
 def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid_iters=32, camera_type="pinhole",
              z_far=10.0, remove_invisible=1, denoise_cloud=1, denoise_nb_points=30, denoise_radius=0.03,
-             get_pc=1) -> dict:
+             get_pc=1, occlusion_check=0, lr_check=0, occlusion_tol=1.0, lr_thresh=1.0) -> dict:
     """scripts/run_demo.py:131-275 for one pair of uint8 frames (arrays or device tensors).  Returns
     device tensors: ``disp`` (H,W), ``vis`` (H,2W,3) uint8, ``minmax`` (2), ``depth`` (H,W), ``cloud`` and
     ``cloud_denoise`` as (points (M,3), colors (M,3) uint8) -- the last three None without ``get_pc``,
-    ``cloud_denoise`` None without ``denoise_cloud`` -- and ``frames``, the ingest result."""
+    ``cloud_denoise`` None without ``denoise_cloud`` -- and ``frames``, the ingest result.  With
+    ``occlusion_check`` or ``lr_check`` (the latter runs a second forward for the right view's
+    disparity), ``visibility`` is ``visibility.classify``'s result, the picture is drawn from the
+    disparity with every other class set to +inf, and only VISIBLE pixels enter the clouds; ``disp``
+    stays the forward's."""
+    check = bool(occlusion_check) or bool(lr_check)
+    if check and camera_type != "pinhole":
+        raise ValueError("run_pair: occlusion_check / lr_check model a rectified pinhole pair (a pixel moves along its "
+                         f"row by its disparity); camera_type {camera_type!r} is refused")
+    if lr_check and hiera:
+        raise ValueError("run_pair: lr_check with hiera is refused: the right view's disparity comes from the plain forward")
     fr = frames.ingest(left_u8, right_u8, scale=scale)
     if len(fr.batch) != 1:
         raise ValueError(f"run_pair: one pair at a time, got a batch of {len(fr.batch)}")
@@ -41,14 +56,26 @@ def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid
         else:
             disp = model.run_hierachical(fr.left, fr.right, iters=valid_iters, test_mode=True, small_ratio=0.5)
     disp = fr.padder.unpad(disp.float())                                    # run_demo.py:166
+    vis_cls, drawn = None, disp
+    if check:
+        from . import visibility
+        right = None
+        if lr_check:
+            right = fr.padder.unpad(visibility.right_disparity(model, fr.left, fr.right, iters=valid_iters).float())
+        vis_cls = visibility.classify(disp, right, occlusion=bool(occlusion_check), occlusion_tol=occlusion_tol,
+                                      lr_thresh=lr_thresh)
+        drawn = visibility.invalidate(disp, vis_cls.classes)
     other = {}
-    vis = frames.vis_disparity(disp[:, 0], image=fr.image_u8, other_output=other)
+    vis = frames.vis_disparity(drawn[:, 0], image=fr.image_u8, other_output=other)
     out = {"disp": disp[0, 0], "vis": vis[0], "minmax": other["minmax"][0], "frames": fr,
            "depth": None, "cloud": None, "cloud_denoise": None}
+    if check:
+        out["visibility"] = vis_cls
     if get_pc:
         c = cloud.disparity_to_cloud(disp, K, baseline, image=fr.image_u8, denoise=bool(denoise_cloud),
                                      nb_points=denoise_nb_points, radius=denoise_radius, scale=scale,
-                                     camera_type=camera_type, remove_invisible=bool(remove_invisible), z_far=z_far)[0]
+                                     camera_type=camera_type, remove_invisible=bool(remove_invisible), z_far=z_far,
+                                     keep=vis_cls.visible if check else None)[0]
         out["depth"] = c.depth
         out["cloud"] = (c.xyz_map[c.valid], fr.image_u8[0][c.valid])
         if denoise_cloud:
@@ -79,6 +106,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--denoise_nb_points", type=int, default=30,
                    help="Number of points to consider for radius outlier removal")
     p.add_argument("--denoise_radius", type=float, default=0.03, help="Radius to use for outlier removal")
+    p.add_argument("--occlusion_check", type=int, default=0,
+                   help="Drop pixels hidden from the right camera (a z-buffer over the disparity) from picture and clouds")
+    p.add_argument("--lr_check", type=int, default=0,
+                   help="Drop pixels that fail the left-right consistency check (costs a second forward)")
+    p.add_argument("--occlusion_tol", type=float, default=1.0,
+                   help="Occluded when another pixel lands on the same right-image column with a disparity this much larger (px)")
+    p.add_argument("--lr_thresh", type=float, default=1.0, help="Left-right disparity difference above which a pixel is dropped (px)")
     p.add_argument("--synthetic", action="store_true",
                    help="No checkpoint: the hash-initialised model of the tests (synth.make_args + synth.init_module_)")
     p.add_argument("--max_disp", type=int, default=192, help="With --synthetic: the model's max_disp")
@@ -108,6 +142,12 @@ def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     if not 0 < a.scale <= 1:
         raise SystemExit("scale must be in (0, 1]")                           # run_demo.py:149
+    check = bool(a.occlusion_check) or bool(a.lr_check)
+    if check and a.camera_type != "pinhole":
+        raise SystemExit("demo: --occlusion_check / --lr_check model a rectified pinhole pair; "
+                         "--camera_type panorama is refused with either")
+    if a.lr_check and a.hiera:
+        raise SystemExit("demo: --lr_check with --hiera 1 is refused: the right view's disparity comes from the plain forward")
     if not torch.cuda.is_available():
         raise SystemExit("demo: needs a HIP device")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -120,7 +160,8 @@ def main(argv=None) -> dict:
     out = run_pair(model, left, right, K, baseline, scale=a.scale, hiera=a.hiera, valid_iters=a.valid_iters,
                    camera_type=a.camera_type, z_far=a.z_far, remove_invisible=a.remove_invisible,
                    denoise_cloud=a.denoise_cloud, denoise_nb_points=a.denoise_nb_points,
-                   denoise_radius=a.denoise_radius, get_pc=a.get_pc)
+                   denoise_radius=a.denoise_radius, get_pc=a.get_pc, occlusion_check=a.occlusion_check,
+                   lr_check=a.lr_check, occlusion_tol=a.occlusion_tol, lr_thresh=a.lr_thresh)
     fr = out["frames"]
     res = {"out_dir": a.out_dir, "image_size": list(out["disp"].shape), "padded_size": list(fr.batch.shape[-2:]),
            "min_disp": float(out["minmax"][0]), "max_disp": float(out["minmax"][1])}
@@ -129,6 +170,12 @@ def main(argv=None) -> dict:
         return os.path.join(a.out_dir, name)
     frames.write_png(path("vis.png"), out["vis"])                             # run_demo.py:168-170
     res["vis"] = path("vis.png")
+    if check:
+        v = out["visibility"]
+        grey = torch.tensor(VISIBILITY_GREY, dtype=torch.uint8, device=device)[v.classes[0].long()]
+        frames.write_png(path("visibility.png"), grey[:, :, None].expand(-1, -1, 3).contiguous())
+        res["visibility_png"] = path("visibility.png")
+        res["visibility"] = [int(n) for n in v.counts[0].cpu().tolist()]      # pixels per class, in code order
     if a.get_pc:
         cloud.write_ply(path("cloud.ply"), *out["cloud"])                     # run_demo.py:255
         res["cloud"], res["cloud_points"] = path("cloud.ply"), int(out["cloud"][0].shape[0])

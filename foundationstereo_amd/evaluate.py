@@ -10,7 +10,9 @@
 
 ``--gt_file`` is a ``.npy`` float map (H,W), or the reference's 3 x uint8 encoding (Utils.py:137-140) as
 an image file or a uint8 ``.npy`` (H,W,3), decoded with ``--gt_scale``.  A pixel is scored where the
-ground truth is positive and finite; ``--all_pixels`` scores every pixel.  ``--error_png`` writes the
+ground truth is positive and finite; ``--all_pixels`` scores every pixel; ``--noc`` scores the non-occluded
+pixels (the benchmarks' headline mask), with the occlusion derived from the ground truth itself
+(``visibility.classify(gt).visible``, ``--occlusion_tol``), and adds ``"mask": "noc"`` to the line.  ``--error_png`` writes the
 error map through the disparity picture's kernels (0 .. ``--error_max`` px over the turbo table,
 unscored pixels black).  ``--per_iter`` scores every refinement iteration in one pass (``losses``): the model
 runs ``forward(test_mode=False)``, each iteration's disparity is unpadded as a view, and the JSON line
@@ -43,6 +45,8 @@ def parser():
     p.add_argument("--gt_scale", default=1000.0, type=float, help="Scale of the uint8 ground-truth encoding")
     p.add_argument("--thresholds", default=[1.0, 3.0, 5.0], type=float, nargs="*", help="Bad-pixel thresholds in px (up to 8)")
     p.add_argument("--all_pixels", action="store_true", help="Score every pixel (a mask of ones), not only gt > 0")
+    p.add_argument("--noc", action="store_true",
+                   help="Score non-occluded pixels only: gt > 0, finite and visible to the right camera by the ground truth's own z-buffer")
     p.add_argument("--error_png", default=None, type=str, help="Write the error map as a PNG here")
     p.add_argument("--error_max", default=5.0, type=float, help="Error in px at the top of the picture's colour range")
     p.add_argument("--per_iter", action="store_true",
@@ -68,6 +72,19 @@ def read_gt(path: str, device) -> torch.Tensor:
     if a.ndim != 3 or a.shape[2] < 3:
         raise SystemExit(f"evaluate: {path}: the uint8 encoding needs 3 channels, got {a.shape}")
     return torch.from_numpy(np.ascontiguousarray(a[:, :, :3])).to(device)
+
+
+def score_mask(a, gt: torch.Tensor, device):
+    """The validity mask (1,H,W) of the flags, or None for the default ``gt > 0`` and finite.  ``--noc``:
+    the VISIBLE class of the ground truth itself (``visibility.classify``: positive, finite, inside the
+    right image, and not behind another pixel of its row by more than ``--occlusion_tol``)."""
+    if a.all_pixels:
+        return torch.ones((1,) + tuple(gt.shape[:2]), dtype=torch.bool, device=device)
+    if a.noc:
+        from . import visibility
+        g = metrics.decode_gt(gt, a.gt_scale) if gt.dtype == torch.uint8 else gt
+        return visibility.classify(g, occlusion_tol=a.occlusion_tol).visible
+    return None
 
 
 def predict(a, device) -> torch.Tensor:
@@ -119,7 +136,7 @@ def per_iter(a, device) -> dict:
     H, W = preds[-1].shape[-2:]
     if tuple(gt.shape[:2]) != (H, W):
         raise SystemExit(f"evaluate: ground truth {tuple(gt.shape[:2])} against a disparity of {(H, W)}")
-    mask = torch.ones((1, H, W), dtype=torch.bool, device=device) if a.all_pixels else None
+    mask = score_mask(a, gt, device)
     m = losses.sequence_metrics(init, preds, gt[None], mask, a.gamma, a.max_disparity, a.thresholds, init_scale=4.0,
                                 gt_scale=a.gt_scale)
     # the fields of the plain call, from the unclamped last iteration: the merged single-map stage on its view
@@ -149,6 +166,8 @@ def per_iter(a, device) -> dict:
                         "init": pick(rows[0]) if init is not None else None, "loss": loss, "gamma": a.gamma,
                         "max_disparity": a.max_disparity, "converged_px": a.converged_px,
                         "first_iter_within": within[0] if within else None}}
+    if a.noc:
+        res["mask"] = "noc"
     print(json.dumps(res))
     return res
 
@@ -157,6 +176,8 @@ def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     if a.scale != 1:
         raise SystemExit("evaluate: --scale must be 1: resizing a ground truth is not defined here")
+    if a.noc and a.all_pixels:
+        raise SystemExit("evaluate: --noc and --all_pixels name two different masks")
     if len(a.thresholds) > metrics.MAX_THRESHOLDS:
         raise SystemExit(f"evaluate: at most {metrics.MAX_THRESHOLDS} thresholds")
     if not torch.cuda.is_available():
@@ -174,8 +195,8 @@ def main(argv=None) -> dict:
     gt = read_gt(a.gt_file, device)
     if tuple(gt.shape[:2]) != tuple(pred.shape):
         raise SystemExit(f"evaluate: ground truth {tuple(gt.shape[:2])} against a disparity of {tuple(pred.shape)}")
-    mask = torch.ones(pred.shape, dtype=torch.bool, device=device) if a.all_pixels else None
-    m = metrics.stereo_metrics(pred, gt, mask, a.thresholds, a.gt_scale, want_error=a.error_png is not None)
+    mask = score_mask(a, gt, device)
+    m = metrics.stereo_metrics(pred, gt, None if mask is None else mask[0], a.thresholds, a.gt_scale, want_error=a.error_png is not None)
     if a.error_png is not None:
         frames.write_png(a.error_png, frames.vis_disparity(m.error, min_val=0.0, max_val=a.error_max)[0])
     row = m.table[0].cpu().tolist()                         # the one read-back
@@ -187,6 +208,8 @@ def main(argv=None) -> dict:
            "pred_min": row[metrics.PRED_MIN], "pred_max": row[metrics.PRED_MAX]}
     if a.error_png is not None:
         res["error_png"] = a.error_png
+    if a.noc:
+        res["mask"] = "noc"
     print(json.dumps(res))
     return res
 

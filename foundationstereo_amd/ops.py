@@ -1264,6 +1264,38 @@ def radius_outlier_mask(points: Tensor, valid: Tensor = None, nb_points: int = 3
     return keep.view(torch.bool)
 
 
+# ---------------------------------------------------------------- visibility
+
+VIS_NCLASS = 5              # FSMI_VIS_NCLASS
+VIS_MAX_W = 8192
+
+
+def disp_visibility(disp: Tensor, disp_right: Tensor = None, occlusion_tol: float = 1.0, lr_thresh: float = 1.0,
+                    occlusion: bool = True, want_error: bool = False):
+    """Occlusion z-buffer and left-right check in one launch (include/fsmi.h for the classes and the
+    arithmetic).  disp (B,H,W), disp_right None or (B,H,W) -> classes (B,H,W) uint8, counts (B,5) int64,
+    error (B,H,W) fp32 or None (``want_error`` needs ``disp_right``).  No host synchronisation."""
+    _check("disp_visibility", disp, *([] if disp_right is None else [disp_right]))
+    if disp.dim() != 3:
+        raise RuntimeError(f"disp_visibility: disp must be (B,H,W), got {tuple(disp.shape)}")
+    B, H, W = disp.shape
+    if disp_right is not None and (disp_right.shape != disp.shape or disp_right.device != disp.device):
+        raise RuntimeError(f"disp_visibility: disp_right must be ({B},{H},{W}) on the device of disp, got "
+                           f"{tuple(disp_right.shape)} on {disp_right.device}")
+    if want_error and disp_right is None:
+        raise RuntimeError("disp_visibility: want_error needs disp_right (the error is the left-right difference)")
+    disp = _c(disp)
+    disp_right = _c(disp_right) if disp_right is not None else None
+    classes = torch.empty((B, H, W), device=disp.device, dtype=torch.uint8)
+    counts = torch.empty((B, VIS_NCLASS), device=disp.device, dtype=torch.int64)
+    error = torch.empty((B, H, W), device=disp.device, dtype=torch.float32) if want_error else None
+    _lib.check(_lib.load().fsmi_disp_visibility(_p(disp), _p(disp_right) if disp_right is not None else None,
+                                                _p(classes), _p(error) if want_error else None, _p(counts), B, H, W,
+                                                float(occlusion_tol), float(lr_thresh), int(bool(occlusion)),
+                                                _stream(disp)), "disp_visibility")
+    return classes, counts, error
+
+
 # ---------------------------------------------------------------- frames in, pictures out
 
 def _check_u8(name: str, *ts: Tensor):

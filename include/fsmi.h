@@ -411,6 +411,53 @@ int fsmi_cloud_cell_keys(const float* points, const unsigned char* valid, long l
 int fsmi_radius_count(const long long* sorted_keys, const long long* perm, const float* sorted_points4,
                       unsigned char* keep, int N, float radius, int nb_points, void* stream);
 
+/* ---- visibility: which disparities belong to pixels the right camera cannot see ----
+ * One class per pixel of a rectified LEFT disparity map, from an occlusion z-buffer over the map
+ * itself and, with a right-view disparity, the left-right consistency check.  Nothing in the reference
+ * pins these definitions (it only drops u - d < 0, scripts/run_demo.py:173-178); they are stated here
+ * and restated in numpy by tests/visibility_oracle.py.  One launch after a memset of counts on the same
+ * stream; no host synchronisation, no allocation, no float atomics; capturable in a hipGraph.
+ *
+ * disp: fp32 (B,H,W), 16-byte aligned.  disp_right: NULL, or fp32 (B,H,W), 16-byte aligned, the RIGHT
+ * view's disparity on the right image's pixel grid.  classes: uint8 (B,H,W), 4-byte aligned.
+ * err: NULL, or fp32 (B,H,W), 16-byte aligned; needs disp_right.  counts: int64 (B, FSMI_VIS_NCLASS),
+ * 8-byte aligned, zeroed by the call itself.  1 <= W <= 8192 (FSMI_ERR_ARG beyond: a row's z-buffer and
+ * right-view row live in LDS, 8 B per column, so a workgroup stays at or below 64 KiB).
+ * occlusion_tol and lr_thresh must not be NaN.
+ * For pixel (u = column, v = row) with d = disp[b][v][u], every operation in un-contracted fp32 and in
+ * this order; the first matching class wins:
+ *   FSMI_VIS_INVALID      d is not finite, or d <= 0
+ *   FSMI_VIS_OUT_OF_VIEW  xr = (float)u - d;  xr < 0                        (run_demo.py:174-178)
+ *   FSMI_VIS_OCCLUDED     only with occlusion != 0:  c = (int)floorf(xr + 0.5f);  zbuf[c] - d > occlusion_tol,
+ *                         zbuf[c] = the largest d over the pixels of the same row that are neither
+ *                         INVALID nor OUT_OF_VIEW and have the same c (0 <= xr <= W - 1 puts c in
+ *                         [0, W - 1]); the pixel itself is among them, so equal disparities on one
+ *                         column occlude nobody
+ *   FSMI_VIS_MISMATCH     only with disp_right (dR = its row v of pair b):
+ *                           x0 = (int)floorf(xr);  t = xr - (float)x0;  x1 = min(x0 + 1, W - 1)
+ *                           r = (t == 0) ? dR[x0] : dR[x0] + t * (dR[x1] - dR[x0])
+ *                           e = fabsf(d - r);  MISMATCH iff !(e <= lr_thresh)   (a non-finite r mismatches)
+ *   FSMI_VIS_VISIBLE      everything else
+ * err[b][v][u] = e for VISIBLE, OCCLUDED and MISMATCH pixels, NaN for INVALID and OUT_OF_VIEW ones.
+ * counts[b][k] = the number of pixels of pair b in class k: integer sums, so equal inputs give equal
+ * bits in all three outputs.
+ * As built: a 256-thread workgroup takes groups of clamp(1024 / W, 1, 8) whole rows of one pair (one
+ * group each while B * groups <= 2048 workgroups, several beyond).  Per group it zeroes the rows'
+ * z-buffer (uint32) in LDS and copies the right-view rows there, splats with an LDS atomicMax on the
+ * bits of d (a positive finite float's bits order like the float, so the maximum is independent of the
+ * order of arrival) and classifies; at its end it adds its class counts with one integer atomic per class.  Loads
+ * and stores are 16 B / 4 B per lane on the pixels whose flat index is a multiple of 4, whatever the row
+ * base; the at most 3 + 3 pixels around them go one by one. */
+#define FSMI_VIS_VISIBLE 0
+#define FSMI_VIS_INVALID 1
+#define FSMI_VIS_OUT_OF_VIEW 2
+#define FSMI_VIS_OCCLUDED 3
+#define FSMI_VIS_MISMATCH 4
+#define FSMI_VIS_NCLASS 5
+int fsmi_disp_visibility(const float* disp, const float* disp_right_or_null, unsigned char* classes,
+                         float* err_or_null, long long* counts, int B, int H, int W,
+                         float occlusion_tol, float lr_thresh, int occlusion, void* stream);
+
 /* ---- around the forward: frame ingest and the disparity picture -----------
  * uint8 frames in, uint8 pictures out (with the cloud section, the exceptions to the all-fp32
  * convention).  Nothing below synchronises the host; all of it can be captured in a hipGraph.
