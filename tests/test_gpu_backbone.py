@@ -17,6 +17,7 @@ import torch.nn.functional as F
 import oracle
 from foundationstereo_amd import backbone as bb, ops, synth
 from oracle import backbone_oracle as bo
+from tests.backbone_reference import sdpa_ref as _sdpa_ref, xca_ref
 from tests.helpers import load_golden, t
 
 pytestmark = pytest.mark.gpu
@@ -57,15 +58,6 @@ def test_channel_layernorm(C, T, n, off):
     out = ops.channel_layernorm(x.to(DEV), w.to(DEV), b.to(DEV), 1e-6, n=n, x_offset=off)
     ref = F.layer_norm(x.double()[:, :, off:off + n].transpose(1, 2), (C,), w.double(), b.double(), 1e-6).transpose(1, 2)
     _close(out, ref, what="layernorm")
-
-
-def _sdpa_ref(qkv, heads, T, scale):
-    B, C3, Tp = qkv.shape
-    hd = C3 // (3 * heads)
-    q, k, v = qkv.double().view(B, 3, heads, hd, Tp).unbind(1)          # (B, heads, hd, Tp)
-    s = torch.einsum("bhdi,bhdj->bhij", q, k[..., :T]) * scale
-    p = torch.softmax(s, -1)
-    return torch.einsum("bhij,bhdj->bhdi", p, v[..., :T]).reshape(B, heads * hd, Tp)
 
 
 # key ranges per (image, head, query tile) (fsmi_vit_attention_ws_floats > 0): 1 (64, 192), 2 (1x16 heads
@@ -152,12 +144,7 @@ def test_xca(C, heads, N):
     qkv = _rand((2, 3 * C, N), 15)
     temp = _rand((heads, 1, 1), 16, 0.5) + 1.0
     out = ops.xca(qkv.to(DEV), temp.to(DEV), heads)
-    B, ch = 2, C // heads
-    q, k, v = qkv.double().view(B, 3, heads, ch, N).unbind(1)
-    q = q / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    k = k / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-    a = torch.softmax(q @ k.transpose(-2, -1) * temp.double(), -1)
-    _close(out, (a @ v).reshape(B, C, N), rel=3e-6, abs_=3e-6, what="xca")
+    _close(out, xca_ref(qkv, temp, heads), rel=3e-6, abs_=3e-6, what="xca")
 
 
 @pytest.mark.parametrize("KS", [3, 5, 7, 9])

@@ -879,6 +879,30 @@ def test_gru_gates_vs_torch(ops_mod):
     close(out, ref, atol=1e-6)
 
 
+def test_gru_gates_saturated(ops_mod):
+    """Gate pre-activations at +-100 (expf overflows to inf in the sigmoid's denominator; sigmoid 0 or 1) and
+    candidate pre-activations at +-100 (tanh +-1): every output finite and within the same 1e-6."""
+    B, Hd, Cx, H, W = 2, 16, 24, 5, 7
+
+    def sign(s, shape):
+        return torch.sign(g(synth.normal(s, shape))) * 100.0
+
+    zr_s, zr_l = (sign(s, (B, 2 * Hd, H, W)) for s in (171, 172))
+    h, x = g(synth.normal(73, (B, Hd, H, W))), g(synth.normal(74, (B, Cx, H, W)))
+    qs_in, ql_in = ops_mod.gru_reset(zr_s, zr_l, h, x)
+    assert bool(torch.isfinite(qs_in).all()) and bool(torch.isfinite(ql_in).all())
+    close(qs_in, torch.cat([torch.sigmoid(zr_s[:, Hd:].double()) * h, x], 1), atol=1e-6)
+    close(ql_in, torch.cat([torch.sigmoid(zr_l[:, Hd:].double()) * h, x], 1), atol=1e-6)
+    q_s, q_l = (sign(s, (B, Hd, H, W)) for s in (175, 176))
+    att = g(synth.uniform(77, (B, 1, H, W)))
+    out = ops_mod.gru_blend(zr_s, zr_l, q_s, q_l, h, att)
+    assert bool(torch.isfinite(out).all())
+    zs, zl = torch.sigmoid(zr_s[:, :Hd].double()), torch.sigmoid(zr_l[:, :Hd].double())
+    hd, ad = h.double(), att.double()
+    ref = ((1 - zs) * hd + zs * torch.tanh(q_s.double())) * ad + ((1 - zl) * hd + zl * torch.tanh(q_l.double())) * (1 - ad)
+    close(out, ref, atol=1e-6)
+
+
 @pytest.mark.parametrize("HW", [(24, 40), (13, 21)])
 def test_selective_gru_fused_vs_oracle(ops_mod, HW):
     """SelectiveConvGRU with the gates in the conv epilogues (zr -> z, r*h; convq -> blend) vs the
@@ -900,9 +924,10 @@ def test_selective_gru_fused_vs_oracle(ops_mod, HW):
     close(out, ref, atol=2e-5)
 
 
-@pytest.mark.parametrize("B,C,H,W", [(1, 128, 120, 160), (2, 128, 13, 70), (1, 40, 5, 3)])
+@pytest.mark.parametrize("B,C,H,W", [(1, 128, 120, 160), (2, 128, 13, 70), (1, 40, 5, 3), (2, 1, 5, 70), (2, 5, 7, 67)])
 def test_conv3x3_cout1_vs_torch(ops_mod, B, C, H, W):
-    """DispHead's last conv (Cin -> 1, 3x3) on its fp32 kernel, + res, written into a channel slice."""
+    """DispHead's last conv (Cin -> 1, 3x3) on its fp32 kernel, + res, written into a channel slice.  With 1
+    and 5 input channels the fourth wave's channel quarter is empty (at 1, the second and third too)."""
     x = g(synth.normal(synth.name_seed(f"c1x{B}{C}{H}"), (B, C, H, W)))
     w = g(synth.normal(synth.name_seed(f"c1w{B}{C}{H}"), (1, C, 3, 3), 0.05))
     bias = g(synth.normal(7, (1,), 0.3))
