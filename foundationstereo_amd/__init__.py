@@ -12,7 +12,10 @@ EPE / RMSE / bad-pixel rates / D1 of a disparity against a ground truth
 refinement iteration scored in one pass, the reference's sequence loss and
 the convergence curve (``evaluate --per_iter``), and ``visibility``: an
 occlusion z-buffer and the left-right check, one class per pixel
-(``demo --occlusion_check``, ``evaluate --noc``).  See DESIGN.md.
+(``demo --occlusion_check``, ``evaluate --noc``), and ``photometric``: does a
+disparity explain the two images, with no ground truth (warp residual, 3x3
+SSIM, a row probe for vertical misalignment; ``demo --photo_check``,
+``evaluate --photometric``).  See DESIGN.md.
 """
 import os as _os
 

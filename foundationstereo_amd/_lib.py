@@ -73,6 +73,9 @@ SIGNATURES = {
     "fsmi_cloud_cell_keys": [_P, _P, _P, _I, _F, _P],
     "fsmi_radius_count": [_P, _P, _P, _P, _I, _F, _I, _P],
     "fsmi_disp_visibility": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P],
+    "fsmi_photo_consistency": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I] + [ctypes.c_longlong] * 8 +
+                              [ctypes.POINTER(_F), _I, ctypes.c_double, _I, _P],
+    "fsmi_photo_consistency_ws_bytes": [_I, _I, _I, _I],
     "fsmi_frames_ingest": [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _I, _I, _I, _P],
     "fsmi_disp_minmax": [_P, _P, _I, _I, _I, _F, _P],
     "fsmi_disp_colorize": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
@@ -147,7 +150,8 @@ def load():
             raise FsmiError(f"{path}: missing symbol {name}")
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name in ("fsmi_last_error", "fsmi_arch") else
-                      ctypes.c_longlong if name.endswith("_floats") and name != "fsmi_dt_layer_floats" else ctypes.c_int)
+                      ctypes.c_longlong if name.endswith("_floats") and name != "fsmi_dt_layer_floats" else
+                      ctypes.c_size_t if name.endswith("_ws_bytes") else ctypes.c_int)
     _lib = lib
     return lib
 

@@ -15,6 +15,7 @@
 //   radius_outlier_mask scripts/run_demo.py:270-273 (Open3D remove_radius_outlier)
 //   disp_visibility     no reference counterpart (occlusion z-buffer, left-right check; include/fsmi.h)
 //   frames_ingest       scripts/run_demo.py:131-159   vis_disparity     Utils.py:108-133
+//   photo_consistency   no reference counterpart (warp residual, 3x3 SSIM, row probe; include/fsmi.h)
 //   disp_metrics        train/utils.py:88-141, train/losses.py:326-339   gt_decode  Utils.py:137-140
 //   seq_metrics         train/losses.py:20-187, :379-498
 #include <torch/library.h>
@@ -486,6 +487,69 @@ std::tuple<Tensor, Tensor, Tensor> seq_metrics(at::TensorList preds_, const Tens
   return {table, sums, loss};
 }
 
+// an image of ops.photo_consistency: a view keeps its strides, only an innermost stride other than 1 is copied
+Tensor photo_image(const char* what, const Tensor& t, bool u8, int64_t B, int64_t H, int64_t W, const Tensor& disp) {
+  if (u8) check_u8("photo_consistency", t); else check_dev("photo_consistency", t);
+  TORCH_CHECK(t.dim() == 4 && t.device() == disp.device() && t.size(0) == B &&
+                  (u8 ? t.size(1) == H && t.size(2) == W : t.size(2) == H && t.size(3) == W),
+              "photo_consistency: ", what, " must be fp32 (B,C,H,W) or uint8 (B,H,W,C) on the device of disp");
+  const int64_t C = u8 ? t.size(3) : t.size(1);
+  TORCH_CHECK(C == 1 || C == 3, "photo_consistency: ", what, " has ", C, " channels: 1 or 3");
+  if (u8) return t.contiguous();
+  const bool view_ok = t.stride(3) == 1 && t.stride(2) >= W && t.stride(1) >= 0 && t.stride(0) >= 0;
+  return view_ok ? t : t.contiguous();
+}
+
+// ops.photo_consistency: (table, sums, warped, l1, dssim); a map not asked for has no element
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> photo_consistency(const Tensor& disp_, const Tensor& left_,
+                                                                     const Tensor& right_,
+                                                                     const c10::optional<Tensor>& mask_,
+                                                                     at::ArrayRef<double> row_offsets, double alpha,
+                                                                     bool want_warped, bool want_l1, bool want_dssim) {
+  const c10::DeviceGuard guard(disp_.device());
+  check_dev("photo_consistency", disp_);
+  Tensor disp = disp_;
+  if (disp.dim() == 2) disp = disp.unsqueeze(0);
+  else if (disp.dim() == 4 && disp.size(1) == 1) disp = disp.select(1, 0);
+  TORCH_CHECK(disp.dim() == 3, "photo_consistency: disp must be (H,W), (B,H,W) or (B,1,H,W)");
+  const int64_t B = disp.size(0), H = disp.size(1), W = disp.size(2);
+  const bool u8 = left_.scalar_type() == at::kByte;
+  Tensor left = photo_image("left", left_, u8, B, H, W, disp), right = photo_image("right", right_, u8, B, H, W, disp);
+  const int64_t C = u8 ? left.size(3) : left.size(1);
+  TORCH_CHECK(C == (u8 ? right.size(3) : right.size(1)), "photo_consistency: left and right differ in channels");
+  TORCH_CHECK((int64_t)row_offsets.size() <= FSMI_PHOTO_MAX_OFFSETS, "photo_consistency: at most ",
+              FSMI_PHOTO_MAX_OFFSETS, " row offsets");
+  Tensor mask;
+  if (mask_.has_value() && mask_->defined()) {
+    TORCH_CHECK(mask_->is_cuda() && mask_->device() == disp.device() &&
+                    (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
+                    mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
+                "photo_consistency: mask must be bool or uint8 (B,H,W) on the device of disp");
+    mask = mask_->contiguous().view(at::kByte);
+  }
+  if (!(disp.stride(2) == 1 && disp.stride(1) >= W && disp.stride(0) >= 0)) disp = disp.contiguous();
+  const int R = (int)row_offsets.size(), NT = FSMI_PHOTO_NFIXED + 2 * R;
+  const auto f64 = disp.options().dtype(at::kDouble);
+  const int64_t ws_doubles = (int64_t)(fsmi_photo_consistency_ws_bytes((int)B, (int)H, (int)W, R) / sizeof(double));
+  Tensor ws = at::empty({ws_doubles > 0 ? ws_doubles : 1}, f64);
+  Tensor table = at::empty({B, NT}, f64), sums = at::empty({B, NT}, f64);
+  Tensor warped = want_warped ? at::empty({B, C, H, W}, disp.options()) : at::empty({0}, disp.options());
+  Tensor l1 = want_l1 ? at::empty({B, H, W}, disp.options()) : at::empty({0}, disp.options());
+  Tensor dssim = want_dssim ? at::empty({B, H, W}, disp.options()) : at::empty({0}, disp.options());
+  float offs[FSMI_PHOTO_MAX_OFFSETS] = {};
+  for (int k = 0; k < R; ++k) offs[k] = (float)row_offsets[k];
+  ok(fsmi_photo_consistency(cp(disp), left.data_ptr(), right.data_ptr(), mask.defined() ? mask.data_ptr<uint8_t>() : nullptr,
+                            want_warped ? mp(warped) : nullptr, want_l1 ? mp(l1) : nullptr,
+                            want_dssim ? mp(dssim) : nullptr, table.data_ptr<double>(), sums.data_ptr<double>(),
+                            ws.data_ptr<double>(), (int)B, (int)C, (int)H, (int)W,
+                            u8 ? FSMI_IMAGE_U8_HWC : FSMI_IMAGE_F32_PLANAR, disp.stride(0), disp.stride(1),
+                            u8 ? 0 : left.stride(0), u8 ? 0 : left.stride(1), u8 ? 0 : left.stride(2),
+                            u8 ? 0 : right.stride(0), u8 ? 0 : right.stride(1), u8 ? 0 : right.stride(2), offs, R, alpha,
+                            1, stream_of(disp)),
+     "photo_consistency");
+  return {table, sums, warped, l1, dssim};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(fsmi, m) {
@@ -507,6 +571,10 @@ TORCH_LIBRARY(fsmi, m) {
   // visibility classes (include/fsmi.h): (classes, counts, error); error is empty unless want_error
   m.def("disp_visibility(Tensor disp, Tensor? disp_right, float occlusion_tol, float lr_thresh, bool occlusion, "
         "bool want_error) -> (Tensor, Tensor, Tensor)");
+  // photometric consistency (include/fsmi.h): (table, sums, warped, l1, dssim); a map not asked for is empty
+  m.def("photo_consistency(Tensor disp, Tensor left, Tensor right, Tensor? mask=None, float[] row_offsets=[], "
+        "float alpha=0.85, bool want_warped=False, bool want_l1=True, bool want_dssim=True) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor)");
   // around the forward (scripts/run_demo.py:131-170): (batch, image_u8) and (picture, minmax)
   m.def("frames_ingest(Tensor left, Tensor right, float scale=1.0, int divis_by=32) -> (Tensor, Tensor)");
   // invalid_thres=None is +inf, the reference's default (the schema grammar has no literal for it)
@@ -537,6 +605,7 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("disp_to_xyz", disp_to_xyz);
   m.impl("radius_outlier_mask", radius_outlier_mask);
   m.impl("disp_visibility", disp_visibility);
+  m.impl("photo_consistency", photo_consistency);
   m.impl("frames_ingest", frames_ingest);
   m.impl("vis_disparity", vis_disparity);
   m.impl("disp_metrics", disp_metrics);

@@ -10,7 +10,11 @@ Frames in (``frames.ingest``), forward, picture (``frames.vis_disparity``), dept
 names and defaults (run_demo.py:45-80); ``--out_dir`` is honoured (the reference replaces it with a
 timestamped folder) and no viewer window opens.  ``--occlusion_check 1`` and ``--lr_check 1`` (not in the
 reference; ``visibility``) draw the picture and build the clouds from the VISIBLE pixels only, write
-``visibility.png`` and add the five class counts to the JSON line.  ``--synthetic`` runs without a checkpoint on the
+``visibility.png`` and add the five class counts to the JSON line.  ``--photo_check 1`` (not in the reference;
+``photometric``) scores the disparity against the two frames without a ground truth: it writes ``warped.png``
+(the right frame in the left view) and ``photometric.png`` (the residual, 0 .. ``--photo_max`` grey levels) and
+adds ``"photometric"`` and ``"row_offset"``, the rig's vertical misalignment probed over -2 .. 2 rows, to the
+line.  ``--synthetic`` runs without a checkpoint on the
 hash-initialised model the tests use.
 """
 from __future__ import annotations
@@ -32,7 +36,7 @@ VISIBILITY_GREY = (255, 0, 64, 128, 192)
 
 def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid_iters=32, camera_type="pinhole",
              z_far=10.0, remove_invisible=1, denoise_cloud=1, denoise_nb_points=30, denoise_radius=0.03,
-             get_pc=1, occlusion_check=0, lr_check=0, occlusion_tol=1.0, lr_thresh=1.0) -> dict:
+             get_pc=1, occlusion_check=0, lr_check=0, occlusion_tol=1.0, lr_thresh=1.0, photo_check=0) -> dict:
     """scripts/run_demo.py:131-275 for one pair of uint8 frames (arrays or device tensors).  Returns
     device tensors: ``disp`` (H,W), ``vis`` (H,2W,3) uint8, ``minmax`` (2), ``depth`` (H,W), ``cloud`` and
     ``cloud_denoise`` as (points (M,3), colors (M,3) uint8) -- the last three None without ``get_pc``,
@@ -40,8 +44,13 @@ def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid
     ``occlusion_check`` or ``lr_check`` (the latter runs a second forward for the right view's
     disparity), ``visibility`` is ``visibility.classify``'s result, the picture is drawn from the
     disparity with every other class set to +inf, and only VISIBLE pixels enter the clouds; ``disp``
-    stays the forward's."""
+    stays the forward's.  With ``photo_check``, ``photometric`` is ``photometric.consistency``'s result (with the
+    warped frame and the maps, over the VISIBLE pixels when a check is on) and ``row_probe``
+    ``photometric.row_probe``'s over -2 .. 2 rows."""
     check = bool(occlusion_check) or bool(lr_check)
+    if photo_check and camera_type != "pinhole":
+        raise ValueError("run_pair: photo_check warps a rectified pinhole pair (a pixel moves along its row by its "
+                         f"disparity); camera_type {camera_type!r} is refused")
     if check and camera_type != "pinhole":
         raise ValueError("run_pair: occlusion_check / lr_check model a rectified pinhole pair (a pixel moves along its "
                          f"row by its disparity); camera_type {camera_type!r} is refused")
@@ -71,6 +80,11 @@ def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid
            "depth": None, "cloud": None, "cloud_denoise": None}
     if check:
         out["visibility"] = vis_cls
+    if photo_check:
+        from . import photometric
+        lv, rv, keep = fr.padder.unpad(fr.left), fr.padder.unpad(fr.right), vis_cls.visible if check else None
+        out["photometric"] = photometric.consistency(disp, lv, rv, keep, want_warped=True)
+        out["row_probe"] = photometric.row_probe(disp, lv, rv, keep, max_offset=2.0, step=1.0)
     if get_pc:
         c = cloud.disparity_to_cloud(disp, K, baseline, image=fr.image_u8, denoise=bool(denoise_cloud),
                                      nb_points=denoise_nb_points, radius=denoise_radius, scale=scale,
@@ -113,6 +127,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--occlusion_tol", type=float, default=1.0,
                    help="Occluded when another pixel lands on the same right-image column with a disparity this much larger (px)")
     p.add_argument("--lr_thresh", type=float, default=1.0, help="Left-right disparity difference above which a pixel is dropped (px)")
+    p.add_argument("--photo_check", type=int, default=0,
+                   help="Score the disparity against the two frames: warped.png, photometric.png, residual and row offset in the JSON line")
+    p.add_argument("--photo_max", type=float, default=32.0, help="Residual in grey levels at the top of photometric.png's colour range")
     p.add_argument("--synthetic", action="store_true",
                    help="No checkpoint: the hash-initialised model of the tests (synth.make_args + synth.init_module_)")
     p.add_argument("--max_disp", type=int, default=192, help="With --synthetic: the model's max_disp")
@@ -138,6 +155,14 @@ def load_model(a, device):
     return model
 
 
+def photo_summary(ph, b: int = 0) -> dict:
+    """The JSON object of pair ``b`` of a ``photometric.consistency`` result (one read-back)."""
+    from . import photometric as pm
+    row = ph.table[b, :pm.NFIXED].cpu().tolist()
+    return {"l1_mean": row[pm.L1_MEAN], "l1_rms": row[pm.L1_RMS], "dssim_mean": row[pm.DSSIM_MEAN],
+            "photometric": row[pm.PHOTOMETRIC], "n_scored": int(row[pm.N_SCORED]), "n_ssim": int(row[pm.N_SSIM])}
+
+
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     if not 0 < a.scale <= 1:
@@ -146,6 +171,8 @@ def main(argv=None) -> dict:
     if check and a.camera_type != "pinhole":
         raise SystemExit("demo: --occlusion_check / --lr_check model a rectified pinhole pair; "
                          "--camera_type panorama is refused with either")
+    if a.photo_check and a.camera_type != "pinhole":
+        raise SystemExit("demo: --photo_check warps a rectified pinhole pair; --camera_type panorama is refused with it")
     if a.lr_check and a.hiera:
         raise SystemExit("demo: --lr_check with --hiera 1 is refused: the right view's disparity comes from the plain forward")
     if not torch.cuda.is_available():
@@ -161,7 +188,8 @@ def main(argv=None) -> dict:
                    camera_type=a.camera_type, z_far=a.z_far, remove_invisible=a.remove_invisible,
                    denoise_cloud=a.denoise_cloud, denoise_nb_points=a.denoise_nb_points,
                    denoise_radius=a.denoise_radius, get_pc=a.get_pc, occlusion_check=a.occlusion_check,
-                   lr_check=a.lr_check, occlusion_tol=a.occlusion_tol, lr_thresh=a.lr_thresh)
+                   lr_check=a.lr_check, occlusion_tol=a.occlusion_tol, lr_thresh=a.lr_thresh,
+                   photo_check=a.photo_check)
     fr = out["frames"]
     res = {"out_dir": a.out_dir, "image_size": list(out["disp"].shape), "padded_size": list(fr.batch.shape[-2:]),
            "min_disp": float(out["minmax"][0]), "max_disp": float(out["minmax"][1])}
@@ -176,6 +204,14 @@ def main(argv=None) -> dict:
         frames.write_png(path("visibility.png"), grey[:, :, None].expand(-1, -1, 3).contiguous())
         res["visibility_png"] = path("visibility.png")
         res["visibility"] = [int(n) for n in v.counts[0].cpu().tolist()]      # pixels per class, in code order
+    if a.photo_check:
+        ph, probe = out["photometric"], out["row_probe"]
+        frames.write_png(path("warped.png"), ph.warped[0].clamp(0, 255).permute(1, 2, 0).to(torch.uint8).contiguous())
+        frames.write_png(path("photometric.png"), frames.vis_disparity(ph.l1, min_val=0.0, max_val=a.photo_max)[0])
+        res["warped_png"], res["photometric_png"] = path("warped.png"), path("photometric.png")
+        res["photometric"] = photo_summary(ph)
+        off = float(probe.offset[0])
+        res["row_offset"] = off if off == off else None                         # NaN: the minimum is not bracketed
     if a.get_pc:
         cloud.write_ply(path("cloud.ply"), *out["cloud"])                     # run_demo.py:255
         res["cloud"], res["cloud_points"] = path("cloud.ply"), int(out["cloud"][0].shape[0])

@@ -21,7 +21,12 @@ iteration), the initial disparity's row (``init``: resized to full size and mult
 sequence ``loss`` and ``first_iter_within``, the first iteration whose EPE is within ``--converged_px`` of
 the last one's; the other fields stay those of the last iteration.  With ``--per_iter``, ``--pred_file``
 names a stored sequence (K,H,W).  The model flags are the demo's (``demo.parser``); ``--scale`` must stay 1,
-because resizing a ground truth is not defined here.  Prints one JSON line.
+because resizing a ground truth is not defined here.  ``--photometric`` and ``--row_probe N`` score the
+disparity against the two frames instead (``photometric``: the right frame warped by the disparity, its
+residual, and the residual with the right frame N rows up and down): they add ``"photometric"`` and
+``"row_probe"`` objects to the line, need ``--left_file`` and ``--right_file`` and no ground truth (``--gt_file`` may be
+left out with either; the line then has no ground-truth fields).  With ``--noc`` their mask is the visible
+set.  Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -38,7 +43,7 @@ def parser():
     p = demo.parser()
     p.prog = "python -m foundationstereo_amd.evaluate"
     p.description = "Score a disparity (the model's, or a stored map) against a ground truth"
-    p.add_argument("--gt_file", required=True, type=str,
+    p.add_argument("--gt_file", default=None, type=str,
                    help="Ground truth: .npy float map (H,W), or the 3 x uint8 encoding as an image / uint8 .npy (H,W,3)")
     p.add_argument("--pred_file", default=None, type=str,
                    help="Score this stored .npy disparity instead of running the model on --left_file / --right_file")
@@ -55,7 +60,17 @@ def parser():
                    help="With --per_iter: first_iter_within reports the first iteration whose EPE is this close to the last one's")
     p.add_argument("--gamma", default=0.9, type=float, help="With --per_iter: the sequence loss's weight factor")
     p.add_argument("--max_disparity", default=192.0, type=float, help="With --per_iter: the sequence loss clamps to [0, this]")
+    p.add_argument("--photometric", action="store_true",
+                   help="Score the disparity against the two frames (warp residual, SSIM); needs no --gt_file")
+    p.add_argument("--row_probe", default=0, type=int,
+                   help="Probe the rig's vertical misalignment over the integer row offsets -N..N (0 = off, at most 3)")
     return p
+
+
+def _given(argv, flag: str) -> bool:
+    """Whether ``flag`` is on the command line (the demo's defaults name files of the reference's assets)."""
+    args = sys.argv[1:] if argv is None else argv
+    return any(x == flag or x.startswith(flag + "=") for x in args)
 
 
 def read_gt(path: str, device) -> torch.Tensor:
@@ -172,8 +187,42 @@ def per_iter(a, device) -> dict:
     return res
 
 
+def photo_fields(a, pred: torch.Tensor, mask, device) -> dict:
+    """--photometric / --row_probe: the objects they add to the line.  ``pred`` (H,W); the frames are read
+    again (as the forward's ingest did) and go in as uint8; ``mask`` (1,H,W) or None."""
+    from . import photometric
+
+    def frame(path):                                    # uint8 (H,W) or (H,W,3): alpha dropped, as the ingest does
+        x = frames.read_image(path)
+        if x.ndim == 3:
+            x = x[:, :, :3] if x.shape[2] >= 3 else x[:, :, 0]
+        return torch.from_numpy(np.ascontiguousarray(x)).to(device)
+    left, right = frame(a.left_file), frame(a.right_file)
+    if tuple(left.shape[:2]) != tuple(pred.shape) or left.shape != right.shape:
+        raise SystemExit(f"evaluate: frames {tuple(left.shape)} and {tuple(right.shape)} against a disparity of {tuple(pred.shape)}")
+    res = {}
+    if a.photometric:
+        res["photometric"] = demo.photo_summary(photometric.consistency(pred, left, right, mask, want_maps=False))
+    if a.row_probe:
+        p = photometric.row_probe(pred, left, right, mask, max_offset=float(a.row_probe), step=1.0)
+        flat = torch.cat([p.l1[0], p.offset]).cpu().tolist()                       # the one read-back
+        res["row_probe"] = {"offsets": [int(o) for o in p.offsets.tolist()], "l1": flat[:-1],
+                            "offset": flat[-1] if flat[-1] == flat[-1] else None}
+    return res
+
+
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
+    photo = a.photometric or a.row_probe != 0
+    if a.gt_file is None and not photo:
+        raise SystemExit("evaluate: the following arguments are required: --gt_file (optional only with --photometric / --row_probe)")
+    if not 0 <= a.row_probe <= 3:
+        raise SystemExit("evaluate: --row_probe N probes the offsets -N..N, at most 8 of them: N in 0..3")
+    if photo and a.pred_file is not None and not (_given(argv, "--left_file") and _given(argv, "--right_file")):
+        raise SystemExit("evaluate: --photometric / --row_probe with --pred_file need --left_file and --right_file: the "
+                         "residual is between the two frames")
+    if photo and a.per_iter:
+        raise SystemExit("evaluate: --photometric / --row_probe score one disparity: not with --per_iter")
     if a.scale != 1:
         raise SystemExit("evaluate: --scale must be 1: resizing a ground truth is not defined here")
     if a.noc and a.all_pixels:
@@ -192,6 +241,20 @@ def main(argv=None) -> dict:
         pred = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).to(device)
     else:
         pred = predict(a, device)
+    if a.gt_file is None:
+        # no ground truth: --noc takes the visible set of the disparity itself
+        if a.all_pixels or a.error_png is not None:
+            raise SystemExit("evaluate: --all_pixels and --error_png need --gt_file")
+        mask = None
+        if a.noc:
+            from . import visibility
+            mask = visibility.classify(pred, occlusion_tol=a.occlusion_tol).visible
+        res = {"mode": "pred_file" if a.pred_file is not None else "model", "image_size": list(pred.shape)}
+        res.update(photo_fields(a, pred, mask, device))
+        if a.noc:
+            res["mask"] = "noc"
+        print(json.dumps(res))
+        return res
     gt = read_gt(a.gt_file, device)
     if tuple(gt.shape[:2]) != tuple(pred.shape):
         raise SystemExit(f"evaluate: ground truth {tuple(gt.shape[:2])} against a disparity of {tuple(pred.shape)}")
@@ -210,6 +273,8 @@ def main(argv=None) -> dict:
         res["error_png"] = a.error_png
     if a.noc:
         res["mask"] = "noc"
+    if photo:
+        res.update(photo_fields(a, pred, mask, device))
     print(json.dumps(res))
     return res
 

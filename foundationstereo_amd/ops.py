@@ -1296,6 +1296,86 @@ def disp_visibility(disp: Tensor, disp_right: Tensor = None, occlusion_tol: floa
     return classes, counts, error
 
 
+# ---------------------------------------------------------------- photometric consistency
+
+PHOTO_NFIXED = 8            # FSMI_PHOTO_NFIXED
+PHOTO_MAX_OFFSETS = 8       # FSMI_PHOTO_MAX_OFFSETS
+IMAGE_F32_PLANAR, IMAGE_U8_HWC = 0, 1
+
+
+def _photo_image(name: str, t: Tensor, u8: bool, B: int, H: int, W: int, dev):
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise RuntimeError(f"photo_consistency: {name} must be fp32 (B,C,H,W) or uint8 (B,H,W,C)")
+    (_check_u8 if u8 else _check)("photo_consistency", t)
+    C = t.shape[3] if u8 else t.shape[1]
+    if tuple(t.shape) != ((B, H, W, C) if u8 else (B, C, H, W)) or C not in (1, 3) or t.device != dev:
+        raise RuntimeError(f"photo_consistency: {name} must be fp32 ({B},C,{H},{W}) or uint8 ({B},{H},{W},C) with C in "
+                           f"(1, 3) on the device of disp, got {t.dtype} {tuple(t.shape)}")
+    if u8:
+        return t.contiguous(), C
+    # a view goes in as it is: only an innermost stride other than 1 (or a row stride below W) is copied
+    return (t if t.stride(3) == 1 and t.stride(2) >= W and min(t.stride()) >= 0 else t.contiguous()), C
+
+
+def photo_consistency(disp: Tensor, left: Tensor, right: Tensor, mask: Tensor = None, row_offsets=(), alpha: float = 0.85,
+                      want_warped: bool = False, want_l1: bool = True, want_dssim: bool = True, ssim: bool = True):
+    """The right frame warped into the left view by ``disp``, its residual against the left frame (mean
+    absolute difference, 3x3 SSIM) and the absolute difference at up to 8 vertical offsets of the right
+    frame, in two launches and without a host synchronisation (include/fsmi.h has the definitions and
+    the layout of the two rows).  disp fp32 (H,W), (B,H,W) or (B,1,H,W); left, right both fp32 (B,C,H,W)
+    (strided views pass through) or both uint8 (B,H,W,C), C in (1, 3), grey levels 0..255; mask None or
+    bool / uint8 (B,H,W) -> (table (B, 8 + 2R) fp64, sums likewise, warped (B,C,H,W) or None, l1 (B,H,W) or
+    None, dssim (B,H,W) or None).  ``ssim=False`` skips the SSIM columns (they read 0)."""
+    _check("photo_consistency", disp)
+    if disp.dim() == 2:
+        disp = disp[None]
+    elif disp.dim() == 4 and disp.shape[1] == 1:
+        disp = disp[:, 0]
+    if disp.dim() != 3:
+        raise RuntimeError(f"photo_consistency: disp must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(disp.shape)}")
+    B, H, W = disp.shape
+    if not isinstance(left, torch.Tensor) or not isinstance(right, torch.Tensor):
+        raise TypeError("photo_consistency: expected tensors")
+    u8 = left.dtype == torch.uint8
+    left, C = _photo_image("left", left, u8, B, H, W, disp.device)
+    right, Cr = _photo_image("right", right, u8, B, H, W, disp.device)
+    if C != Cr:
+        raise RuntimeError(f"photo_consistency: left has {C} channels and right {Cr}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("photo_consistency: mask must be a bool or uint8 tensor")
+        _check_u8("photo_consistency", mask.view(torch.uint8))
+        if tuple(mask.shape) != (B, H, W) or mask.device != disp.device:
+            raise RuntimeError(f"photo_consistency: mask must be ({B},{H},{W}) on the device of disp, got {tuple(mask.shape)}")
+        mask = mask.contiguous().view(torch.uint8)
+    offs = [float(o) for o in row_offsets]
+    if len(offs) > PHOTO_MAX_OFFSETS:
+        raise RuntimeError(f"photo_consistency: {len(offs)} row offsets, at most {PHOTO_MAX_OFFSETS}")
+    if want_dssim and not ssim:
+        raise RuntimeError("photo_consistency: want_dssim needs ssim")
+    if not (disp.stride(2) == 1 and disp.stride(1) >= W and disp.stride(0) >= 0) and disp.numel():
+        disp = disp.contiguous()
+    lib = _lib.load()
+    dev = disp.device
+    R = len(offs)
+    ws = torch.empty((max(int(lib.fsmi_photo_consistency_ws_bytes(B, H, W, R)) // 8, 1),), device=dev, dtype=torch.float64)
+    table = torch.empty((B, PHOTO_NFIXED + 2 * R), device=dev, dtype=torch.float64)
+    sums = torch.empty((B, PHOTO_NFIXED + 2 * R), device=dev, dtype=torch.float64)
+    warped = torch.empty((B, C, H, W), device=dev, dtype=torch.float32) if want_warped else None
+    l1 = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_l1 else None
+    dssim = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_dssim else None
+    ls = (0, 0, 0) if u8 else left.stride()[:3]
+    rs = (0, 0, 0) if u8 else right.stride()[:3]
+    coffs = (ctypes.c_float * max(R, 1))(*offs)
+    _lib.check(lib.fsmi_photo_consistency(_p(disp), _p(left), _p(right), _p(mask) if mask is not None else None,
+                                          _p(warped) if want_warped else None, _p(l1) if want_l1 else None,
+                                          _p(dssim) if want_dssim else None, _p(table), _p(sums), _p(ws), B, C, H, W,
+                                          IMAGE_U8_HWC if u8 else IMAGE_F32_PLANAR, disp.stride(0), disp.stride(1),
+                                          ls[0], ls[1], ls[2], rs[0], rs[1], rs[2], coffs, R, float(alpha),
+                                          int(bool(ssim)), _stream(disp)), "photo_consistency")
+    return table, sums, warped, l1, dssim
+
+
 # ---------------------------------------------------------------- frames in, pictures out
 
 def _check_u8(name: str, *ts: Tensor):

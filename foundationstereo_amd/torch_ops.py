@@ -24,7 +24,8 @@ _loaded = False
 
 OPS = ("gwc_volume", "concat_volume", "allpairs_corr", "volume_pyramid", "geo_lookup", "bilinear_sampler_1d",
        "disparity_regression", "softmax_regression", "context_upsample", "softmax_context_upsample",
-       "disp_to_xyz", "radius_outlier_mask", "disp_visibility", "frames_ingest", "vis_disparity", "disp_metrics",
+       "disp_to_xyz", "radius_outlier_mask", "disp_visibility", "photo_consistency",
+       "frames_ingest", "vis_disparity", "disp_metrics",
        "gt_decode", "seq_metrics")
 
 

@@ -19,6 +19,8 @@
 #ifndef FSMI_H_
 #define FSMI_H_
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -457,6 +459,87 @@ int fsmi_radius_count(const long long* sorted_keys, const long long* perm, const
 int fsmi_disp_visibility(const float* disp, const float* disp_right_or_null, unsigned char* classes,
                          float* err_or_null, long long* counts, int B, int H, int W,
                          float occlusion_tol, float lr_thresh, int occlusion, void* stream);
+
+/* ---- photometric consistency: does a disparity explain the two images, without a ground truth ----
+ * The right frame warped into the left view by a rectified LEFT disparity, the residual between the
+ * left frame and the warp (mean absolute difference, 3x3 SSIM) and, for a few vertical offsets of the
+ * right frame, the same absolute difference (the row probe: the offset with the smallest residual is
+ * the rig's vertical misalignment).  Nothing in the reference pins these definitions; they are stated
+ * here and restated in numpy by tests/photometric_oracle.py.  Two launches (tiles, then one workgroup
+ * per pair); no host synchronisation, no allocation, no float atomics; capturable in a hipGraph.
+ *
+ * disp: fp32 (B,H,W) with batch and row strides in elements, innermost stride 1, 4-byte aligned.
+ * left, right: both in image_format, C = 1 or 3 channels, values are grey levels 0..255:
+ *   FSMI_IMAGE_F32_PLANAR  fp32 (B,C,H,W) with batch, channel and row strides in elements, innermost
+ *                          stride 1, 4-byte aligned (a view of a padded batch goes in as it is)
+ *   FSMI_IMAGE_U8_HWC      contiguous uint8 (B,H,W,C); the six image strides are ignored
+ * Row strides must be at least W and no stride negative.  mask: NULL, or contiguous uint8 (B,H,W).
+ * warped: NULL, or fp32 (B,C,H,W); l1, dssim: NULL, or fp32 (B,H,W); all contiguous and 16-byte aligned
+ * (FSMI_ERR_ARG otherwise).  A NULL map costs no store.  row_offsets: n_offsets <= FSMI_PHOTO_MAX_OFFSETS
+ * finite fp32 values in HOST memory, read before the call returns.  0 <= alpha <= 1.  ssim != 0 computes
+ * the SSIM columns (and the one-pixel halo they need); ssim == 0 leaves them 0 and refuses a dssim map.
+ * 1 <= B <= 65535, H * W <= 2^31 - 1; there is no cap on W (nothing is staged by whole rows).
+ *
+ * Every per-pixel operation is un-contracted fp32 in the order written, divisions IEEE.  For pixel
+ * (u = column, v = row) with d = disp[b][v][u], L = left, R = right (as fp32 grey levels):
+ *   INVALID      d is not finite, or d <= 0
+ *   OUT OF VIEW  otherwise, xr = (float)u - d;  xr < 0
+ *   SAMPLED      otherwise;   SCORED = SAMPLED and (mask == NULL or mask[b][v][u] != 0)
+ * The sample of channel c at row offset dy (the main path is dy = 0, where w = h(v)):
+ *   x0 = floorf(xr), t = xr - x0, x1 = min(x0 + 1, W - 1)
+ *   h(y) = (t == 0) ? R[c][y][x0] : R[c][y][x0] + t * (R[c][y][x1] - R[c][y][x0])
+ *   yr = (float)v + dy; the pixel counts for that offset only if 0 <= yr <= (float)(H - 1);
+ *   y0 = floorf(yr), ty = yr - y0, y1 = min(y0 + 1, H - 1);  w = (ty == 0) ? h(y0) : h(y0) + ty * (h(y1) - h(y0))
+ *   l1(dy) = |L[0] - w[0]|                                         C = 1
+ *          = ((|L[0] - w[0]| + |L[1] - w[1]|) + |L[2] - w[2]|) / 3.0f    C = 3
+ * warped[b][c][v][u] = w at dy = 0 for SAMPLED pixels, 0 elsewhere.  l1[b][v][u] = l1(0) for SCORED pixels,
+ * +inf elsewhere.
+ * SSIM is defined for a SCORED pixel with 1 <= u <= W - 2, 1 <= v <= H - 2 whose nine 3x3 neighbours are
+ * all SAMPLED (masked in or not).  Per channel, x_k = L and y_k = warped at the taps k = 0..8 in row-major
+ * order ((v-1,u-1), (v-1,u), ... (v+1,u+1)), every sum starting from its k = 0 term and adding k = 1..8 in
+ * order:
+ *   mx = (sum x_k) / 9.0f,  my likewise
+ *   vx = (sum (x_k - mx) * (x_k - mx)) / 9.0f,  vy likewise,  cxy = (sum (x_k - mx) * (y_k - my)) / 9.0f
+ *   num = ((2.0f * mx) * my + 6.5025f) * (2.0f * cxy + 58.5225f)
+ *   den = ((mx * mx + my * my) + 6.5025f) * ((vx + vy) + 58.5225f)
+ *   ds  = (1.0f - num / den) * 0.5f;  if !(ds >= 0) ds = 0;  if (ds > 1) ds = 1
+ * dssim[b][v][u] = ds for C = 1, ((ds[0] + ds[1]) + ds[2]) / 3.0f for C = 3; +inf where SSIM is undefined.
+ * (The variance is the centred two-pass form: E[x^2] - E[x]^2 cancels at 255^2.)
+ *
+ * sums, table: fp64 (B, FSMI_PHOTO_NFIXED + 2 * n_offsets), 8-byte aligned.  Per-pixel values are widened
+ * to fp64 before they are added (l1 * l1 is formed in fp64); counts are exact doubles.
+ *   sums[b]  = [n_scored, n_ssim, n_invalid, n_out_of_view, sum l1, sum l1^2 (both over SCORED pixels),
+ *               sum dssim, sum l1 (both over SSIM pixels), then per offset r: n_r, sum l1(dy_r)]
+ *              n_r counts the SCORED pixels whose yr is in range
+ *   table[b] = [n_scored, n_ssim, n_invalid, n_out_of_view, sums[4] / n_scored, sqrt(sums[5] / n_scored),
+ *               sums[6] / n_ssim, (alpha * sums[6] + ((1 - alpha) * sums[7]) / 255) / n_ssim,
+ *               then per offset r: n_r, sum / n_r]       in fp64; a mean over zero pixels is 0
+ * Column 7, "photometric", is the mean over the SSIM pixels of alpha * dssim + (1 - alpha) * l1 / 255.
+ * workspace: fsmi_photo_consistency_ws_bytes(B, H, W, n_offsets) bytes (0 for arguments the call would
+ * refuse), 8-byte aligned; every row is written, none is read before it is.  The order of every addition
+ * is a function of (B, H, W, n_offsets) alone: a workgroup's 256 lanes reduce through a fixed shuffle
+ * tree and LDS into one stored row per tile, the second launch adds a pair's rows in index order.
+ * Equal inputs give equal bits.
+ * As built: a 256-thread workgroup takes a 64 x 12 tile of one pair.  It reads disp and left once for
+ * the tile and, with SSIM, a one-pixel halo, 16 B per lane (4 B for uint8 C = 1, 12 B for C = 3) on
+ * the quads of columns 4k .. 4k+3 whose address is 16-byte (uint8: 4-byte) aligned, one by one
+ * elsewhere; gathers the right taps from global memory (neighbouring pixels' taps share cache lines);
+ * keeps left, warped, xr and the class in LDS, so each warped value is computed once and the nine
+ * windows that hold it read it from LDS; then scores the tile's own pixels and stores the maps
+ * 16 B per lane under the same rule.  The row probe re-gathers the right taps per offset in the same
+ * launch; the left image and disp are not read again. */
+#define FSMI_IMAGE_F32_PLANAR 0
+#define FSMI_IMAGE_U8_HWC 1
+#define FSMI_PHOTO_NFIXED 8
+#define FSMI_PHOTO_MAX_OFFSETS 8
+int fsmi_photo_consistency(const float* disp, const void* left, const void* right, const unsigned char* mask_or_null,
+                           float* warped_or_null, float* l1_or_null, float* dssim_or_null, double* table, double* sums,
+                           double* workspace, int B, int C, int H, int W, int image_format, long long disp_batch_stride,
+                           long long disp_row_stride, long long left_batch_stride, long long left_channel_stride,
+                           long long left_row_stride, long long right_batch_stride, long long right_channel_stride,
+                           long long right_row_stride, const float* row_offsets, int n_offsets, double alpha, int ssim,
+                           void* stream);
+size_t fsmi_photo_consistency_ws_bytes(int B, int H, int W, int n_offsets);
 
 /* ---- around the forward: frame ingest and the disparity picture -----------
  * uint8 frames in, uint8 pictures out (with the cloud section, the exceptions to the all-fp32
