@@ -35,18 +35,6 @@ class Cloud:
     inliers: Tensor             # (H,W) bool: ``valid`` after the radius outlier removal
 
 
-def _as_bhw(disp: Tensor) -> Tensor:
-    if not isinstance(disp, torch.Tensor):
-        raise TypeError("disparity: expected a tensor")
-    if disp.dim() == 4 and disp.shape[1] == 1:
-        return disp[:, 0]
-    if disp.dim() == 3:
-        return disp
-    if disp.dim() == 2:
-        return disp[None]
-    raise ValueError(f"disparity must be (B,1,H,W), (B,H,W) or (H,W), got {tuple(disp.shape)}")
-
-
 def _camera(K, scale: float):
     K = np.array(K, dtype=np.float32).reshape(3, 3)     # a copy: the caller's K stays as it is
     K[:2] *= scale                                      # scripts/run_demo.py:232
@@ -63,8 +51,8 @@ def disparity_to_xyz(disp: Tensor, K, baseline: float, *, scale: float = 1.0, ca
     of ``disp`` such as ``visibility.classify(disp).visible``, is ANDed into ``valid`` after the kernel;
     ``xyz_map`` and ``depth`` stay as they are.  No host synchronisation."""
     fx, fy, cx, cy = _camera(K, scale)
-    xyz, depth, valid = ops.disp_to_xyz(_as_bhw(disp), fx, fy, cx, cy, baseline, zmin=zmin, z_far=z_far,
-                                        remove_invisible=remove_invisible, camera_type=camera_type)
+    xyz, depth, valid = ops.disp_to_xyz(ops._as_bhw(disp, "disparity_to_xyz", "disp"), fx, fy, cx, cy, baseline,
+                                        zmin=zmin, z_far=z_far, remove_invisible=remove_invisible, camera_type=camera_type)
     if keep is not None:
         if not isinstance(keep, torch.Tensor) or keep.dtype != torch.bool or keep.shape != valid.shape \
                 or keep.device != valid.device:

@@ -240,8 +240,6 @@ __global__ __launch_bounds__(256) void radius_count_kernel(const long long* __re
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 }  // namespace fsmi
 
@@ -261,7 +259,7 @@ int fsmi_disp_to_xyz(const float* disp, float* xyz, float* depth, unsigned char*
                  "fsmi_disp_to_xyz: camera_type %d", camera_type);
   FSMI_CHECK_ARG(camera_type == FSMI_CAMERA_PANORAMA || (fx != 0.f && fy != 0.f && std::isfinite(fx) && std::isfinite(fy)),
                  "fsmi_disp_to_xyz: fx, fy must be finite and nonzero");
-  FSMI_CHECK_ARG(aligned16(disp) && aligned16(xyz) && aligned16(depth) && (reinterpret_cast<uintptr_t>(valid) & 3u) == 0,
+  FSMI_CHECK_ARG(aligned(disp, 16) && aligned(xyz, 16) && aligned(depth, 16) && aligned(valid, 4),
                  "fsmi_disp_to_xyz: disp, xyz, depth must be 16-byte aligned and valid 4-byte aligned");
   Camera cam{fx, fy, cx, cy, baseline, zmin, z_far, remove_invisible != 0, camera_type == FSMI_CAMERA_PANORAMA};
   const long long nthreads = (P >> 2) + ((P & 3) ? 1 : 0);
@@ -289,7 +287,7 @@ int fsmi_radius_count(const long long* sorted_keys, const long long* perm, const
   FSMI_CHECK_ARG(nb_points >= 0, "fsmi_radius_count: nb_points = %d", nb_points);
   if (N == 0) return FSMI_OK;
   FSMI_CHECK_ARG(sorted_keys && perm && sorted_points4 && keep, "fsmi_radius_count: null pointer");
-  FSMI_CHECK_ARG(aligned16(sorted_points4), "fsmi_radius_count: sorted_points4 must be 16-byte aligned");
+  FSMI_CHECK_ARG(aligned(sorted_points4, 16), "fsmi_radius_count: sorted_points4 must be 16-byte aligned");
   hipLaunchKernelGGL(radius_count_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, as_stream(stream), sorted_keys, perm,
                      reinterpret_cast<const float4*>(sorted_points4), keep, N, radius * radius, nb_points);
   return finish_launch("fsmi_radius_count");

@@ -270,8 +270,6 @@ __global__ __launch_bounds__(256) void disp_colorize_kernel(const float* __restr
   }
 }
 
-inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
-
 }  // namespace
 }  // namespace fsmi
 

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <functional>
 #include <string>
@@ -113,6 +114,11 @@ inline int finish_launch(const char* what) {
 }
 
 inline unsigned ceil_div(long long a, long long b) { return static_cast<unsigned>((a + b - 1) / b); }
+
+// p is a multiple of a, a power of two; a null pointer is aligned
+__host__ __device__ __forceinline__ bool aligned(const void* p, uintptr_t a) {
+  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
+}
 
 // XCD-aware block remap: the dispatcher deals blocks round-robin over the 8
 // XCDs (MI355X_MICROARCH.md, workgroup dispatch), so block b and b+8 share an

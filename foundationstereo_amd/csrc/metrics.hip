@@ -4,8 +4,8 @@
 // in Python and synchronise the host 4 + K times per pair).  Here: one streaming pass and a tiny
 // second kernel, no host synchronisation, no allocation, capturable in a hipGraph.
 //   disp_metrics_partial   grid (NB, B): a block reduces its pixels of pair b into one row of 17 doubles
-//                          and STORES it (no float atomics: the order of every addition is fixed by
-//                          (H*W, NB) alone, so the same input gives the same bits on any device)
+//                          and STORES it (the fixed-order reduction of metrics_common.h; here the order
+//                          of every addition is a function of (H*W, NB) alone)
 //   disp_metrics_finalize  one block per pair: sums the NB rows in a fixed order, writes the raw
 //                          accumulators and the table of metrics
 //   gt_decode              the reference's 3 x uint8 ground-truth encoding (Utils.py:137-140) -> fp32
@@ -38,31 +38,13 @@ struct Metrics {
 __device__ __forceinline__ double nan_min(double a, double b) { return (b < a || b != b) ? b : a; }
 __device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
 
-__device__ __forceinline__ double combine(int slot, double a, double b) {
-  return slot == A_MIN ? nan_min(a, b) : slot == A_MAX ? nan_max(a, b) : a + b;
-}
-
-// The 256 lanes' rows of NACC values -> one row: lane s < NACC returns slot s (the others 0).  A
-// shuffle tree inside each wave, then waves 0..3 in index order: the order of the additions is a
-// function of the lane index alone.
-__device__ __forceinline__ double block_reduce(double (&v)[NACC], double (*lds)[NACC]) {
-#pragma unroll
-  for (int s = 0; s < NACC; ++s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[s] = combine(s, v[s], __shfl_down(v[s], off, 64));
+// the reduction's combine (metrics_common.h): the two extreme slots by comparison, every other one a sum
+struct Combine {
+  __device__ __forceinline__ double operator()(int slot, double a, double b) const {
+    return slot == A_MIN ? nan_min(a, b) : slot == A_MAX ? nan_max(a, b) : a + b;
   }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int s = 0; s < NACC; ++s) lds[threadIdx.x >> 6][s] = v[s];
-  }
-  __syncthreads();
-  double r = 0.0;
-  if (threadIdx.x < NACC) {
-    const int s = threadIdx.x;
-    r = combine(s, combine(s, combine(s, lds[0][s], lds[1][s]), lds[2][s]), lds[3][s]);
-  }
-  return r;
-}
+};
+constexpr Combine combine{};
 
 // One lane's running row.  Counts stay below 2^32 per lane (a pair has at most 2^31 - 1 pixels).
 struct Lane {
@@ -108,8 +90,7 @@ __global__ __launch_bounds__(256) void disp_metrics_partial_kernel(const float* 
   const int b = blockIdx.y;
   const long long P = g.P, start = b * P;
   const float* p = pred + start;
-  const float* gtf = U8GT ? nullptr : static_cast<const float*>(gt_any) + start;
-  const unsigned char* gtu = U8GT ? static_cast<const unsigned char*>(gt_any) + 3 * start : nullptr;
+  const GroundTruth<U8GT> gt(gt_any, start, g.gt_scale);
   const unsigned char* mk = mask ? mask + start : nullptr;
   float* er = error ? error + start : nullptr;
   const bool has_mask = mask != nullptr;
@@ -122,31 +103,21 @@ __global__ __launch_bounds__(256) void disp_metrics_partial_kernel(const float* 
 
   Lane a;
   auto one = [&](long long i) {                                      // pixel i of the pair, i < P
-    const float gt = U8GT ? decode_gt(gtu[3 * i], gtu[3 * i + 1], gtu[3 * i + 2], g.gt_scale) : gtf[i];
-    const float e = take(a, p[i], gt, has_mask, has_mask ? mk[i] : 0, x0, g);
+    const float gti = gt[i];
+    const float e = take(a, p[i], gti, has_mask, has_mask ? mk[i] : 0, x0, g);
     if (er) er[i] = e;
   };
   if (t < head) one(t);
   for (long long q = t; q < nquad; q += stride) {
     const long long i = head + (q << 2);
     const float4 x = *reinterpret_cast<const float4*>(p + i);
-    float gt[4];
-    if (U8GT) {
-      const uint3 w = *reinterpret_cast<const uint3*>(gtu + 3 * i);   // 12 bytes: r g b r | g b r g | b r g b
-      gt[0] = decode_gt(w.x & 255u, (w.x >> 8) & 255u, (w.x >> 16) & 255u, g.gt_scale);
-      gt[1] = decode_gt(w.x >> 24, w.y & 255u, (w.y >> 8) & 255u, g.gt_scale);
-      gt[2] = decode_gt((w.y >> 16) & 255u, w.y >> 24, w.z & 255u, g.gt_scale);
-      gt[3] = decode_gt((w.z >> 8) & 255u, (w.z >> 16) & 255u, w.z >> 24, g.gt_scale);
-    } else {
-      const float4 g4 = *reinterpret_cast<const float4*>(gtf + i);
-      gt[0] = g4.x; gt[1] = g4.y; gt[2] = g4.z; gt[3] = g4.w;
-    }
+    const float4 g4 = gt.quad(i);
     const unsigned m4 = has_mask ? *reinterpret_cast<const unsigned*>(mk + i) : 0u;
     float4 e;
-    e.x = take(a, x.x, gt[0], has_mask, m4 & 255u, x0, g);
-    e.y = take(a, x.y, gt[1], has_mask, (m4 >> 8) & 255u, x0, g);
-    e.z = take(a, x.z, gt[2], has_mask, (m4 >> 16) & 255u, x0, g);
-    e.w = take(a, x.w, gt[3], has_mask, m4 >> 24, x0, g);
+    e.x = take(a, x.x, g4.x, has_mask, m4 & 255u, x0, g);
+    e.y = take(a, x.y, g4.y, has_mask, (m4 >> 8) & 255u, x0, g);
+    e.z = take(a, x.z, g4.z, has_mask, (m4 >> 16) & 255u, x0, g);
+    e.w = take(a, x.w, g4.w, has_mask, m4 >> 24, x0, g);
     if (er) *reinterpret_cast<float4*>(er + i) = e;
   }
   if (tail + t < P) one(tail + t);
@@ -156,13 +127,13 @@ __global__ __launch_bounds__(256) void disp_metrics_partial_kernel(const float* 
   v[A_SX] = a.sx; v[A_SX2] = a.sx2; v[A_MIN] = a.mn; v[A_MAX] = a.mx;
 #pragma unroll
   for (int k = 0; k < MAXT; ++k) v[A_BAD + k] = a.bad[k];
-  const double r = block_reduce(v, lds);
+  const double r = block_reduce(v, lds, combine);
   if (threadIdx.x < NACC)
     partials[(static_cast<long long>(b) * gridDim.x + blockIdx.x) * NACC + threadIdx.x] = r;
 }
 
 // One block per pair.  Lane t sums rows t, t + 256, ... (in index order) of the pair's NB partial
-// rows, then the same fixed tree as above.  Lane 0 turns the accumulators into the table.
+// rows, then the same block_reduce.  Lane 0 turns the accumulators into the table.
 __global__ __launch_bounds__(256) void disp_metrics_finalize_kernel(const double* __restrict__ partials,
                                                                     const float* __restrict__ pred,
                                                                     double* __restrict__ sums,
@@ -179,7 +150,7 @@ __global__ __launch_bounds__(256) void disp_metrics_finalize_kernel(const double
 #pragma unroll
     for (int s = 0; s < NACC; ++s) v[s] = combine(s, v[s], src[s]);
   }
-  const double r = block_reduce(v, lds);
+  const double r = block_reduce(v, lds, combine);
   if (threadIdx.x < NACC) {
     sums[b * NACC + threadIdx.x] = r;
     row[threadIdx.x] = r;
@@ -213,19 +184,11 @@ __global__ __launch_bounds__(256) void gt_decode_kernel(const unsigned char* __r
   if (q > nquad) return;
   const long long i = q << 2;
   if (q < nquad) {
-    const uint3 w = *reinterpret_cast<const uint3*>(u8 + 3 * i);
-    float4 o;
-    o.x = decode_gt(w.x & 255u, (w.x >> 8) & 255u, (w.x >> 16) & 255u, gt_scale);
-    o.y = decode_gt(w.x >> 24, w.y & 255u, (w.y >> 8) & 255u, gt_scale);
-    o.z = decode_gt((w.y >> 16) & 255u, w.y >> 24, w.z & 255u, gt_scale);
-    o.w = decode_gt((w.z >> 8) & 255u, (w.z >> 16) & 255u, w.z >> 24, gt_scale);
-    *reinterpret_cast<float4*>(out + i) = o;
+    *reinterpret_cast<float4*>(out + i) = decode_gt4(u8 + 3 * i, gt_scale);
   } else {
     for (long long k = i; k < N; ++k) out[k] = decode_gt(u8[3 * k], u8[3 * k + 1], u8[3 * k + 2], gt_scale);
   }
 }
-
-inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
 }  // namespace
 }  // namespace fsmi
@@ -244,22 +207,15 @@ int fsmi_disp_metrics_blocks(int H, int W) {
 int fsmi_disp_metrics(const float* pred, const float* gt, const unsigned char* gt_u8, const unsigned char* mask,
                       const float* thresholds, int K, double gt_scale, double* partials, double* sums, double* table,
                       float* error, int B, int H, int W, void* stream) {
-  FSMI_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "fsmi_disp_metrics: bad shape (%d,%d,%d)", B, H, W);
-  FSMI_CHECK_ARG(K >= 0 && K <= MAXT, "fsmi_disp_metrics: K = %d thresholds: 0..%d", K, MAXT);
-  FSMI_CHECK_ARG(K == 0 || thresholds, "fsmi_disp_metrics: null thresholds with K = %d", K);
-  FSMI_CHECK_ARG((gt != nullptr) != (gt_u8 != nullptr), "fsmi_disp_metrics: exactly one of gt (fp32) and gt_u8");
-  FSMI_CHECK_ARG(!gt_u8 || gt_scale > 0.0, "fsmi_disp_metrics: gt_scale = %g must be positive", gt_scale);
+  Metrics g;
+  if (const int e = check_scoring_args("fsmi_disp_metrics", B, H, W, gt, gt_u8, gt_scale, thresholds, K, g.thr)) return e;
   FSMI_CHECK_ARG(pred && partials && sums && table, "fsmi_disp_metrics: null pointer");
-  const long long P = static_cast<long long>(H) * W;
-  FSMI_CHECK_ARG(P <= INT_MAX, "fsmi_disp_metrics: H*W = %lld exceeds 2^31 - 1", P);
   FSMI_CHECK_ARG(aligned(pred, 16) && (!gt || aligned(gt, 16)) && (!gt_u8 || aligned(gt_u8, 4)) &&
                      (!mask || aligned(mask, 4)) && (!error || aligned(error, 16)) && aligned(partials, 8) &&
                      aligned(sums, 8) && aligned(table, 8),
                  "fsmi_disp_metrics: fp32 maps must be 16-byte, uint8 maps 4-byte, fp64 outputs 8-byte aligned");
-  Metrics g;
-  g.P = P;
+  g.P = static_cast<long long>(H) * W;
   g.gt_scale = gt_scale;
-  for (int k = 0; k < MAXT; ++k) g.thr[k] = k < K ? thresholds[k] : INFINITY;
   const int NB = fsmi_disp_metrics_blocks(H, W);
   hipStream_t s = as_stream(stream);
   if (gt_u8)
@@ -268,7 +224,7 @@ int fsmi_disp_metrics(const float* pred, const float* gt, const unsigned char* g
   else
     hipLaunchKernelGGL(disp_metrics_partial_kernel<false>, dim3(NB, B), dim3(256), 0, s, pred,
                        static_cast<const void*>(gt), mask, partials, error, g);
-  hipLaunchKernelGGL(disp_metrics_finalize_kernel, dim3(B), dim3(256), 0, s, partials, pred, sums, table, NB, P);
+  hipLaunchKernelGGL(disp_metrics_finalize_kernel, dim3(B), dim3(256), 0, s, partials, pred, sums, table, NB, g.P);
   return finish_launch("fsmi_disp_metrics");
 }
 

@@ -7,15 +7,14 @@
 //             bilinear tap of the right row; left, warped, xr and the class go to LDS.  Each warped
 //             value is computed once here and shared by the up to nine windows that hold it.
 //     score   the tile's own pixels from LDS: warped / l1 / dssim maps out, the row probe's taps, and
-//             the block's sums: shuffle tree per wave, the four waves through LDS in index order, one
-//             row of doubles STORED to the workspace (no float atomics)
+//             the block's sums (block_reduce of metrics_common.h): one row of doubles STORED to the workspace
 //   photo_finalize  one block per pair adds the tiles' rows in index order and writes sums and table
 // The right image is gathered from global memory: a row's taps land on u - d, next to their
 // neighbours', so a wave's taps of one row share cache lines and the rows of a tile stay in L2.
 #include <climits>
 #include <cstdint>
 
-#include "fsmi_common.h"
+#include "metrics_common.h"
 
 namespace fsmi {
 namespace {
@@ -41,8 +40,6 @@ struct Params {
   float dy[MAXOFF];
 };
 
-__device__ __forceinline__ bool al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // element i of an image row as a grey level
 template <int FMT>
 __device__ __forceinline__ float px(const void* base, long long i) {
@@ -58,26 +55,6 @@ __device__ __forceinline__ float tap(const void* img, long long row, int x0, int
   const float a = px<FMT>(img, row + static_cast<long long>(x0) * PS);
   if (t == 0.f) return a;
   return a + t * (px<FMT>(img, row + static_cast<long long>(x1) * PS) - a);
-}
-
-template <int N>
-__device__ __forceinline__ double block_reduce(double (&v)[N], double (*lds)[NACC_MAX]) {
-#pragma unroll
-  for (int s = 0; s < N; ++s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[s] += __shfl_down(v[s], off, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int s = 0; s < N; ++s) lds[threadIdx.x >> 6][s] = v[s];
-  }
-  __syncthreads();
-  double r = 0.0;
-  if (threadIdx.x < N) {
-    const int s = threadIdx.x;
-    r = ((lds[0][s] + lds[1][s]) + lds[2][s]) + lds[3][s];
-  }
-  return r;
 }
 
 template <int FMT, int C, bool SSIM, bool PROBE>
@@ -120,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
 
     float d[4] = {}, L[C][4] = {};
     const float* dp = disp + b * p.disp_bs + v * p.disp_rs + u0;
-    if (full && al(dp, 16)) {
+    if (full && aligned(dp, 16)) {
       const float4 q = *reinterpret_cast<const float4*>(dp);
       d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
     } else {
@@ -130,13 +107,14 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
     }
     if constexpr (U8) {
       const unsigned char* lp = static_cast<const unsigned char*>(left) + lb + v * p.l_rs + static_cast<long long>(u0) * C;
-      if (full && al(lp, 4)) {
+      if (full && aligned(lp, 4)) {
         if constexpr (C == 3) {
-          const uint3 w = *reinterpret_cast<const uint3*>(lp);                 // r g b r | g b r g | b r g b
-          L[0][0] = w.x & 255u; L[1][0] = (w.x >> 8) & 255u; L[2][0] = (w.x >> 16) & 255u;
-          L[0][1] = w.x >> 24; L[1][1] = w.y & 255u; L[2][1] = (w.y >> 8) & 255u;
-          L[0][2] = (w.y >> 16) & 255u; L[1][2] = w.y >> 24; L[2][2] = w.z & 255u;
-          L[0][3] = (w.z >> 8) & 255u; L[1][3] = (w.z >> 16) & 255u; L[2][3] = w.z >> 24;
+          unsigned px4[4][3];
+          unpack_rgb4(*reinterpret_cast<const uint3*>(lp), px4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) L[c][j] = px4[j][c];
         } else {
           const unsigned w = *reinterpret_cast<const unsigned*>(lp);
           L[0][0] = w & 255u; L[0][1] = (w >> 8) & 255u; L[0][2] = (w >> 16) & 255u; L[0][3] = w >> 24;
@@ -152,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         const float* lp = static_cast<const float*>(left) + lb + c * p.l_cs + v * p.l_rs + u0;
-        if (full && al(lp, 16)) {
+        if (full && aligned(lp, 16)) {
           const float4 q = *reinterpret_cast<const float4*>(lp);
           L[c][0] = q.x; L[c][1] = q.y; L[c][2] = q.z; L[c][3] = q.w;
         } else {
@@ -216,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
     unsigned m4 = 0x01010101u;
     if (mask) {
       const unsigned char* mp = mask + o;
-      if (n == 4 && al(mp, 4)) {
+      if (n == 4 && aligned(mp, 4)) {
         m4 = *reinterpret_cast<const unsigned*>(mp);
       } else {
         m4 = 0;
@@ -326,7 +304,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         float* wp = warped + ((static_cast<long long>(b) * C + c) * H + v) * W + u0;
-        if (quad && al(wp, 16)) {
+        if (quad && aligned(wp, 16)) {
           *reinterpret_cast<float4*>(wp) = *reinterpret_cast<const float4*>(&Ws[c][lr][lc0]);
         } else {
           for (int j = 0; j < n; ++j) wp[j] = Ws[c][lr][lc0 + j];
@@ -335,7 +313,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
     }
     if (l1map) {
       float* q = l1map + o;
-      if (quad && al(q, 16)) *reinterpret_cast<float4*>(q) = make_float4(l1v[0], l1v[1], l1v[2], l1v[3]);
+      if (quad && aligned(q, 16)) *reinterpret_cast<float4*>(q) = make_float4(l1v[0], l1v[1], l1v[2], l1v[3]);
       else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -344,7 +322,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
     }
     if (SSIM && dsmap) {
       float* q = dsmap + o;
-      if (quad && al(q, 16)) *reinterpret_cast<float4*>(q) = make_float4(dsv[0], dsv[1], dsv[2], dsv[3]);
+      if (quad && aligned(q, 16)) *reinterpret_cast<float4*>(q) = make_float4(dsv[0], dsv[1], dsv[2], dsv[3]);
       else {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -367,7 +345,7 @@ __global__ __launch_bounds__(kThreads) void photo_tile_kernel(const float* __res
 }
 
 // One block per pair.  Lane t adds the rows t, t + 256, ... of the pair's NB tile rows in index order,
-// then the same fixed tree as above; lane 0 turns the sums into the table.
+// then the same block_reduce; lane 0 turns the sums into the table.
 __global__ __launch_bounds__(kThreads) void photo_finalize_kernel(const double* __restrict__ partials,
                                                                   double* __restrict__ sums, double* __restrict__ table,
                                                                   long long NB, int n_offsets, double alpha) {
@@ -405,8 +383,6 @@ __global__ __launch_bounds__(kThreads) void photo_finalize_kernel(const double* 
     o[NFIX + 2 * k + 1] = nr > 0.0 ? row[NFIX + 2 * k + 1] / nr : 0.0;
   }
 }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 inline long long tiles_of(int H, int W, int* tiles_x) {
   const long long tx = (W + TW - 1) / TW, ty = (H + TH - 1) / TH;

@@ -118,15 +118,6 @@ __device__ __forceinline__ void take(Lane& a, float v, float gt, bool valid, con
   for (int k = 0; k < MAXT; ++k) a.bad[k] += (valid && e > g.thr[k]) ? 1u : 0u;
 }
 
-// the wave's 64 rows of NACC values -> lane 0's: a shuffle tree, its order a function of the lane index alone
-__device__ __forceinline__ void wave_reduce(double (&v)[NACC]) {
-#pragma unroll
-  for (int s = 0; s < NACC; ++s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[s] += __shfl_down(v[s], off, 64);
-  }
-}
-
 template <bool U8GT>
 __global__ __launch_bounds__(256) void seq_metrics_partial_kernel(SeqRows rows, const void* __restrict__ gt_any,
                                                                   const unsigned char* __restrict__ mask,
@@ -136,8 +127,7 @@ __global__ __launch_bounds__(256) void seq_metrics_partial_kernel(SeqRows rows, 
   const int first = blockIdx.y * kRowsPerBlock;                       // within this launch
   const int nr = min(kRowsPerBlock, g.nrows - first);
   const long long P = g.P, start = b * P;
-  const float* gtf = U8GT ? nullptr : static_cast<const float*>(gt_any) + start;
-  const unsigned char* gtu = U8GT ? static_cast<const unsigned char*>(gt_any) + 3 * start : nullptr;
+  const GroundTruth<U8GT> gts(gt_any, start, g.gt_scale);
   const unsigned char* mk = mask ? mask + start : nullptr;
   const bool has_mask = mask != nullptr;
   const unsigned W = static_cast<unsigned>(g.W);
@@ -150,7 +140,7 @@ __global__ __launch_bounds__(256) void seq_metrics_partial_kernel(SeqRows rows, 
       const long long i = tile * kTile + j * 256 + threadIdx.x;
       const bool inside = i < P;
       const unsigned ic = inside ? static_cast<unsigned>(i) : 0u;    // a lane past the end re-reads pixel 0
-      const float gt = U8GT ? decode_gt(gtu[3ll * ic], gtu[3ll * ic + 1], gtu[3ll * ic + 2], g.gt_scale) : gtf[ic];
+      const float gt = gts[ic];
       const bool valid = inside && pixel_valid(has_mask, has_mask ? mk[ic] : 0, gt);
       const unsigned y = ic / W, x = ic - y * W;
 #pragma unroll
@@ -229,8 +219,6 @@ __global__ __launch_bounds__(256) void seq_metrics_finalize_kernel(const double*
   loss[b] = acc;
 }
 
-inline bool aligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
-
 }  // namespace
 }  // namespace fsmi
 
@@ -249,18 +237,13 @@ int fsmi_seq_metrics(const float* const* rows, const long long* batch_strides, c
                      const unsigned char* smooth, int R, const float* gt, const unsigned char* gt_u8,
                      const unsigned char* mask, const float* thresholds, int K, double gt_scale, float beta,
                      double* partials, double* sums, double* table, double* loss, int B, int H, int W, void* stream) {
-  FSMI_CHECK_ARG(B >= 1 && B <= 65535 && H >= 1 && W >= 1, "fsmi_seq_metrics: bad shape (%d,%d,%d)", B, H, W);
+  float thr[MAXT];
+  if (const int e = check_scoring_args("fsmi_seq_metrics", B, H, W, gt, gt_u8, gt_scale, thresholds, K, thr)) return e;
   FSMI_CHECK_ARG(R >= 1 && R <= MAXR, "fsmi_seq_metrics: R = %d rows: 1..%d", R, MAXR);
-  FSMI_CHECK_ARG(K >= 0 && K <= MAXT, "fsmi_seq_metrics: K = %d thresholds: 0..%d", K, MAXT);
-  FSMI_CHECK_ARG(K == 0 || thresholds, "fsmi_seq_metrics: null thresholds with K = %d", K);
-  FSMI_CHECK_ARG((gt != nullptr) != (gt_u8 != nullptr), "fsmi_seq_metrics: exactly one of gt (fp32) and gt_u8");
-  FSMI_CHECK_ARG(!gt_u8 || gt_scale > 0.0, "fsmi_seq_metrics: gt_scale = %g must be positive", gt_scale);
   FSMI_CHECK_ARG(beta >= 0.f, "fsmi_seq_metrics: beta = %g must not be negative", static_cast<double>(beta));
   FSMI_CHECK_ARG(rows && batch_strides && row_strides && hs && ws && muls && max_disps && weights && smooth &&
                      partials && sums && table && loss,
                  "fsmi_seq_metrics: null pointer");
-  const long long P = static_cast<long long>(H) * W;
-  FSMI_CHECK_ARG(P <= INT_MAX, "fsmi_seq_metrics: H*W = %lld exceeds 2^31 - 1", P);
   FSMI_CHECK_ARG((!gt || aligned(gt, 4)) && aligned(partials, 8) && aligned(sums, 8) && aligned(table, 8) &&
                      aligned(loss, 8),
                  "fsmi_seq_metrics: fp32 maps must be 4-byte and fp64 outputs 8-byte aligned");
@@ -282,14 +265,14 @@ int fsmi_seq_metrics(const float* const* rows, const long long* batch_strides, c
   for (int row0 = 0; row0 < R; row0 += kRowsPerLaunch) {
     SeqRows d;
     SeqParams g;
-    g.P = P;
+    g.P = static_cast<long long>(H) * W;
     g.gt_scale = gt_scale;
     g.W = W;
     g.R = R;
     g.row0 = row0;
     g.nrows = std::min(kRowsPerLaunch, R - row0);
     g.beta = beta;
-    for (int k = 0; k < MAXT; ++k) g.thr[k] = k < K ? thresholds[k] : INFINITY;
+    std::copy(thr, thr + MAXT, g.thr);
     for (int q = 0; q < kRowsPerLaunch; ++q) {
       const int r = row0 + std::min(q, g.nrows - 1);                   // unused slots repeat the last row; never read
       SeqRow& o = d.r[q];

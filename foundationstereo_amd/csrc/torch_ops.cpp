@@ -368,6 +368,34 @@ Tensor dense_u8(const Tensor& t) {
   return c;
 }
 
+// an optional bool / uint8 (B,H,W) mask on the device of `ref` (named `ref_name` in the message) as a
+// contiguous uint8 view, undefined when there is none; align4 for fsmi_disp_metrics, which reads it a
+// word at a time
+Tensor mask_arg(const char* name, const c10::optional<Tensor>& mask_, int64_t B, int64_t H, int64_t W, const Tensor& ref,
+                const char* ref_name, bool align4) {
+  if (!mask_.has_value() || !mask_->defined()) return Tensor();
+  TORCH_CHECK(mask_->is_cuda() && mask_->device() == ref.device() &&
+                  (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
+                  mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
+              name, ": mask must be bool or uint8 (B,H,W) on the device of ", ref_name);
+  return (align4 ? dense_u8(*mask_) : mask_->contiguous()).view(at::kByte);
+}
+
+// the thresholds of the scoring ops as the fp32 array the C entry points take
+void fill_thresholds(const char* name, at::ArrayRef<double> thresholds, float (&thr)[FSMI_METRICS_MAX_THRESHOLDS]) {
+  TORCH_CHECK((int64_t)thresholds.size() <= FSMI_METRICS_MAX_THRESHOLDS, name, ": at most ", FSMI_METRICS_MAX_THRESHOLDS,
+              " thresholds");
+  for (size_t k = 0; k < thresholds.size(); ++k) thr[k] = (float)thresholds[k];
+}
+
+// a view keeps its strides: a copy only where the innermost stride is not 1, a row stride is below W or
+// a stride is negative
+Tensor row_dense(const Tensor& t, int64_t W) {
+  bool view_ok = t.stride(-1) == 1 && t.stride(-2) >= W;
+  for (int64_t s : t.strides()) view_ok = view_ok && s >= 0;
+  return view_ok ? t : t.contiguous();
+}
+
 // ops.disp_metrics: (table, sums, error); error has no element when want_error is false
 std::tuple<Tensor, Tensor, Tensor> disp_metrics(const Tensor& pred_, const Tensor& gt_, const c10::optional<Tensor>& mask_,
                                                 at::ArrayRef<double> thresholds, double gt_scale, bool want_error) {
@@ -380,24 +408,15 @@ std::tuple<Tensor, Tensor, Tensor> disp_metrics(const Tensor& pred_, const Tenso
   TORCH_CHECK(gt_.device() == pred_.device() && gt_.dim() == (u8 ? 4 : 3) && gt_.size(0) == B && gt_.size(1) == H &&
                   gt_.size(2) == W && (!u8 || gt_.size(3) == 3),
               "disp_metrics: gt must be fp32 (B,H,W) or uint8 (B,H,W,3) on the device of pred");
-  TORCH_CHECK((int64_t)thresholds.size() <= FSMI_METRICS_MAX_THRESHOLDS, "disp_metrics: at most ",
-              FSMI_METRICS_MAX_THRESHOLDS, " thresholds");
+  float thr[FSMI_METRICS_MAX_THRESHOLDS] = {};
+  fill_thresholds("disp_metrics", thresholds, thr);
   TORCH_CHECK(!u8 || gt_scale > 0.0, "disp_metrics: gt_scale must be positive");
-  Tensor mask;
-  if (mask_.has_value() && mask_->defined()) {
-    TORCH_CHECK(mask_->is_cuda() && mask_->device() == pred_.device() &&
-                    (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
-                    mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
-                "disp_metrics: mask must be bool or uint8 (B,H,W) on the device of pred");
-    mask = dense_u8(*mask_).view(at::kByte);
-  }
+  Tensor mask = mask_arg("disp_metrics", mask_, B, H, W, pred_, "pred", true);
   Tensor pred = dense(pred_), gt = u8 ? dense_u8(gt_) : dense(gt_);
   const auto f64 = pred.options().dtype(at::kDouble);
   Tensor partials = at::empty({B, fsmi_disp_metrics_blocks((int)H, (int)W), FSMI_METRICS_NACC}, f64);
   Tensor sums = at::empty({B, FSMI_METRICS_NACC}, f64), table = at::empty({B, FSMI_METRICS_NACC}, f64);
   Tensor error = want_error ? at::empty({B, H, W}, pred.options()) : at::empty({0}, pred.options());
-  float thr[FSMI_METRICS_MAX_THRESHOLDS] = {};
-  for (size_t k = 0; k < thresholds.size(); ++k) thr[k] = (float)thresholds[k];
   ok(fsmi_disp_metrics(cp(pred), u8 ? nullptr : cp(gt), u8 ? gt.data_ptr<uint8_t>() : nullptr,
                        mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, thr, (int)thresholds.size(), gt_scale,
                        partials.data_ptr<double>(), sums.data_ptr<double>(), table.data_ptr<double>(),
@@ -431,8 +450,8 @@ std::tuple<Tensor, Tensor, Tensor> seq_metrics(at::TensorList preds_, const Tens
   TORCH_CHECK(gt_.dim() == (u8 ? 4 : 3) && (!u8 || gt_.size(3) == 3),
               "seq_metrics: gt must be fp32 (B,H,W) or uint8 (B,H,W,3)");
   const int64_t B = gt_.size(0), H = gt_.size(1), W = gt_.size(2);
-  TORCH_CHECK((int64_t)thresholds.size() <= FSMI_METRICS_MAX_THRESHOLDS, "seq_metrics: at most ",
-              FSMI_METRICS_MAX_THRESHOLDS, " thresholds");
+  float thr[FSMI_METRICS_MAX_THRESHOLDS] = {};
+  fill_thresholds("seq_metrics", thresholds, thr);
   TORCH_CHECK(!u8 || gt_scale > 0.0, "seq_metrics: gt_scale must be positive");
   TORCH_CHECK(beta >= 0.0, "seq_metrics: beta must not be negative");
   TORCH_CHECK(!weights_.has_value() || (int64_t)weights_->size() == R, "seq_metrics: one weight per row");
@@ -450,7 +469,7 @@ std::tuple<Tensor, Tensor, Tensor> seq_metrics(at::TensorList preds_, const Tens
     check_dev("seq_metrics", p);
     TORCH_CHECK(p.dim() == 3 && p.size(0) == B && p.size(1) >= 1 && p.size(2) >= 1 && p.device() == gt_.device(),
                 "seq_metrics: row ", r, " must be (B,h,w) on the device of gt");
-    keep.push_back(p.stride(2) == 1 && p.stride(1) >= p.size(2) && p.stride(0) >= 0 ? p : p.contiguous());
+    keep.push_back(row_dense(p, p.size(2)));
     const Tensor& q = keep.back();
     rows.push_back(cp(q));
     bs.push_back(q.stride(0));
@@ -463,21 +482,12 @@ std::tuple<Tensor, Tensor, Tensor> seq_metrics(at::TensorList preds_, const Tens
     TORCH_CHECK(r >= 0 && r < R, "seq_metrics: smooth row ", r, " of ", R, " rows");
     smooth[r] = 1;
   }
-  Tensor mask;
-  if (mask_.has_value() && mask_->defined()) {
-    TORCH_CHECK(mask_->is_cuda() && mask_->device() == gt_.device() &&
-                    (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
-                    mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
-                "seq_metrics: mask must be bool or uint8 (B,H,W) on the device of gt");
-    mask = mask_->contiguous().view(at::kByte);
-  }
+  Tensor mask = mask_arg("seq_metrics", mask_, B, H, W, gt_, "gt", false);
   Tensor gt = gt_.contiguous();
   const auto f64 = gt.options().dtype(at::kDouble);
   Tensor partials = at::empty({B, R, fsmi_seq_metrics_blocks((int)H, (int)W, (int)R), FSMI_SEQ_NACC}, f64);
   Tensor sums = at::empty({B, R, FSMI_SEQ_NACC}, f64), table = at::empty({B, R, FSMI_SEQ_NACC}, f64);
   Tensor loss = at::empty({B}, f64);
-  float thr[FSMI_METRICS_MAX_THRESHOLDS] = {};
-  for (size_t k = 0; k < thresholds.size(); ++k) thr[k] = (float)thresholds[k];
   ok(fsmi_seq_metrics(rows.data(), bs.data(), rs.data(), hs.data(), ws.data(), muls.data(), maxds.data(), weights.data(),
                       smooth.data(), (int)R, u8 ? nullptr : cp(gt), u8 ? gt.data_ptr<uint8_t>() : nullptr,
                       mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, thr, (int)thresholds.size(), gt_scale,
@@ -487,7 +497,7 @@ std::tuple<Tensor, Tensor, Tensor> seq_metrics(at::TensorList preds_, const Tens
   return {table, sums, loss};
 }
 
-// an image of ops.photo_consistency: a view keeps its strides, only an innermost stride other than 1 is copied
+// an image of ops.photo_consistency
 Tensor photo_image(const char* what, const Tensor& t, bool u8, int64_t B, int64_t H, int64_t W, const Tensor& disp) {
   if (u8) check_u8("photo_consistency", t); else check_dev("photo_consistency", t);
   TORCH_CHECK(t.dim() == 4 && t.device() == disp.device() && t.size(0) == B &&
@@ -495,9 +505,7 @@ Tensor photo_image(const char* what, const Tensor& t, bool u8, int64_t B, int64_
               "photo_consistency: ", what, " must be fp32 (B,C,H,W) or uint8 (B,H,W,C) on the device of disp");
   const int64_t C = u8 ? t.size(3) : t.size(1);
   TORCH_CHECK(C == 1 || C == 3, "photo_consistency: ", what, " has ", C, " channels: 1 or 3");
-  if (u8) return t.contiguous();
-  const bool view_ok = t.stride(3) == 1 && t.stride(2) >= W && t.stride(1) >= 0 && t.stride(0) >= 0;
-  return view_ok ? t : t.contiguous();
+  return u8 ? t.contiguous() : row_dense(t, W);
 }
 
 // ops.photo_consistency: (table, sums, warped, l1, dssim); a map not asked for has no element
@@ -519,15 +527,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> photo_consistency(const Tenso
   TORCH_CHECK(C == (u8 ? right.size(3) : right.size(1)), "photo_consistency: left and right differ in channels");
   TORCH_CHECK((int64_t)row_offsets.size() <= FSMI_PHOTO_MAX_OFFSETS, "photo_consistency: at most ",
               FSMI_PHOTO_MAX_OFFSETS, " row offsets");
-  Tensor mask;
-  if (mask_.has_value() && mask_->defined()) {
-    TORCH_CHECK(mask_->is_cuda() && mask_->device() == disp.device() &&
-                    (mask_->scalar_type() == at::kBool || mask_->scalar_type() == at::kByte) && mask_->dim() == 3 &&
-                    mask_->size(0) == B && mask_->size(1) == H && mask_->size(2) == W,
-                "photo_consistency: mask must be bool or uint8 (B,H,W) on the device of disp");
-    mask = mask_->contiguous().view(at::kByte);
-  }
-  if (!(disp.stride(2) == 1 && disp.stride(1) >= W && disp.stride(0) >= 0)) disp = disp.contiguous();
+  Tensor mask = mask_arg("photo_consistency", mask_, B, H, W, disp, "disp", false);
+  disp = row_dense(disp, W);
   const int R = (int)row_offsets.size(), NT = FSMI_PHOTO_NFIXED + 2 * R;
   const auto f64 = disp.options().dtype(at::kDouble);
   const int64_t ws_doubles = (int64_t)(fsmi_photo_consistency_ws_bytes((int)B, (int)H, (int)W, R) / sizeof(double));

@@ -189,8 +189,6 @@ __global__ __launch_bounds__(kThreads) void visibility_kernel(const float* __res
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace fsmi
 

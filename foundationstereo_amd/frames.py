@@ -102,12 +102,8 @@ def vis_disparity(disp: Tensor, min_val: Optional[float] = None, max_val: Option
     passed as ``other_output`` receives the (B,2) device tensor of [min, max] under ``"minmax"``
     (no synchronisation).  Where the reference is undefined: NaN is an invalid pixel, and
     ``max == min`` maps every valid pixel to ``lut[0]``."""
-    if not isinstance(disp, torch.Tensor):
-        raise TypeError("vis_disparity: expected a tensor")
+    d = ops._as_bhw(disp, "vis_disparity", "disp")
     single = disp.dim() == 2
-    d = disp[None] if single else disp[:, 0] if disp.dim() == 4 and disp.shape[1] == 1 else disp
-    if d.dim() != 3:
-        raise ValueError(f"vis_disparity: disp must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(disp.shape)}")
     if lut is None:
         lut = _lut_on.get(d.device)
         if lut is None and d.is_cuda:

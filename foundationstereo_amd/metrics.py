@@ -94,15 +94,7 @@ class StereoMetrics:
 
 
 def _as_bhw(x: Tensor, name: str) -> Tensor:
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"stereo_metrics: {name} must be a tensor")
-    if x.dim() == 2:
-        return x[None]
-    if x.dim() == 4 and x.shape[1] == 1:
-        return x[:, 0]
-    if x.dim() == 3:
-        return x
-    raise ValueError(f"stereo_metrics: {name} must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(x.shape)}")
+    return ops._as_bhw(x, "stereo_metrics", name)
 
 
 def stereo_metrics(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None,

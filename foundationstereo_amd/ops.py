@@ -50,6 +50,84 @@ def _p(t: Tensor) -> int:
     return t.data_ptr()
 
 
+def _check_u8(name: str, *ts: Tensor):
+    """``_check`` for uint8 tensors (frames, LUT, side-by-side image, encoded ground truth, masks)."""
+    for t in ts:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected tensors")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: fsmi ops run on ROCm (HIP) device tensors only; got {t.device}")
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"{name}: expected uint8, got {t.dtype}")
+
+
+def _u8_aligned(t: Tensor) -> Tensor:
+    """Contiguous and 4-byte aligned (the kernels read uint8 maps a word at a time)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 4 == 0 else t.clone()
+
+
+def _row_dense(t: Tensor, W: int) -> Tensor:
+    """A view goes in as it is; a copy only where the innermost stride is not 1, a row stride is below
+    ``W`` or a stride is negative."""
+    return t if t.stride(-1) == 1 and t.stride(-2) >= W and min(t.stride()) >= 0 else t.contiguous()
+
+
+def _as_bhw(x, who: str, name: str, exc=ValueError) -> Tensor:
+    """A map given as (H,W), (B,H,W) or (B,1,H,W) -> its (B,H,W) view; ``who`` prefixes the message."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{who}: {name} must be a tensor")
+    if x.dim() == 2:
+        return x[None]
+    if x.dim() == 4 and x.shape[1] == 1:
+        return x[:, 0]
+    if x.dim() != 3:
+        raise exc(f"{who}: {name} must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(x.shape)}")
+    return x
+
+
+def _mask_arg(name: str, mask, B: int, H: int, W: int, dev, ref_name: str, align4: bool = False):
+    """None, or the bool / uint8 (B,H,W) mask as a contiguous uint8 view.  ``align4``: 4-byte aligned as
+    well, for an entry point that reads the mask a word at a time (fsmi_disp_metrics); the others read
+    bytes, or test the address themselves, and take an odd view without a copy."""
+    if mask is None:
+        return None
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError(f"{name}: mask must be a bool or uint8 tensor")
+    _check_u8(name, mask.view(torch.uint8))
+    if tuple(mask.shape) != (B, H, W) or mask.device != dev:
+        raise RuntimeError(f"{name}: mask must be ({B},{H},{W}) on the device of {ref_name}, got {tuple(mask.shape)}")
+    return (_u8_aligned(mask) if align4 else mask.contiguous()).view(torch.uint8)
+
+
+def _thresholds_arg(name: str, thresholds):
+    """-> (the thresholds as floats, the fp32 array the C entry point takes): rounded to fp32 here,
+    compared in fp32."""
+    thr = [float(t) for t in thresholds]
+    if len(thr) > METRICS_MAX_THRESHOLDS:
+        raise RuntimeError(f"{name}: {len(thr)} thresholds, at most {METRICS_MAX_THRESHOLDS}")
+    return thr, (ctypes.c_float * max(len(thr), 1))(*thr)
+
+
+def _gt_arg(name: str, gt, gt_scale: float, pred: Tensor = None) -> bool:
+    """The ground truth of the scoring ops: fp32 (B,H,W), or uint8 (B,H,W,3) in the reference's encoding
+    with ``gt_scale`` > 0; of ``pred``'s shape and device where one is given.  -> whether it is uint8."""
+    if not isinstance(gt, torch.Tensor):
+        raise TypeError(f"{name}: expected tensors")
+    u8 = gt.dtype == torch.uint8
+    (_check_u8 if u8 else _check)(name, gt)
+    ok = gt.dim() == (4 if u8 else 3) and (not u8 or gt.shape[3] == 3)
+    if pred is not None:
+        ok = ok and tuple(gt.shape[:3]) == tuple(pred.shape) and gt.device == pred.device
+    if not ok:
+        B, H, W = ("B", "H", "W") if pred is None else pred.shape
+        raise RuntimeError(f"{name}: gt must be fp32 ({B},{H},{W}) or uint8 ({B},{H},{W},3)"
+                           f"{'' if pred is None else ' on the device of pred'}, got {gt.dtype} {tuple(gt.shape)}")
+    if u8 and not float(gt_scale) > 0.0:
+        raise RuntimeError(f"{name}: gt_scale = {gt_scale} must be positive")
+    return u8
+
+
 def _overlaps(a: Tensor, b: Tensor) -> bool:
     """Whether the byte ranges a and b span on the same device intersect."""
     if a.device != b.device or a.numel() == 0 or b.numel() == 0:
@@ -1311,10 +1389,7 @@ def _photo_image(name: str, t: Tensor, u8: bool, B: int, H: int, W: int, dev):
     if tuple(t.shape) != ((B, H, W, C) if u8 else (B, C, H, W)) or C not in (1, 3) or t.device != dev:
         raise RuntimeError(f"photo_consistency: {name} must be fp32 ({B},C,{H},{W}) or uint8 ({B},{H},{W},C) with C in "
                            f"(1, 3) on the device of disp, got {t.dtype} {tuple(t.shape)}")
-    if u8:
-        return t.contiguous(), C
-    # a view goes in as it is: only an innermost stride other than 1 (or a row stride below W) is copied
-    return (t if t.stride(3) == 1 and t.stride(2) >= W and min(t.stride()) >= 0 else t.contiguous()), C
+    return (t.contiguous() if u8 else _row_dense(t, W)), C
 
 
 def photo_consistency(disp: Tensor, left: Tensor, right: Tensor, mask: Tensor = None, row_offsets=(), alpha: float = 0.85,
@@ -1327,12 +1402,7 @@ def photo_consistency(disp: Tensor, left: Tensor, right: Tensor, mask: Tensor = 
     bool / uint8 (B,H,W) -> (table (B, 8 + 2R) fp64, sums likewise, warped (B,C,H,W) or None, l1 (B,H,W) or
     None, dssim (B,H,W) or None).  ``ssim=False`` skips the SSIM columns (they read 0)."""
     _check("photo_consistency", disp)
-    if disp.dim() == 2:
-        disp = disp[None]
-    elif disp.dim() == 4 and disp.shape[1] == 1:
-        disp = disp[:, 0]
-    if disp.dim() != 3:
-        raise RuntimeError(f"photo_consistency: disp must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(disp.shape)}")
+    disp = _as_bhw(disp, "photo_consistency", "disp", RuntimeError)
     B, H, W = disp.shape
     if not isinstance(left, torch.Tensor) or not isinstance(right, torch.Tensor):
         raise TypeError("photo_consistency: expected tensors")
@@ -1341,20 +1411,13 @@ def photo_consistency(disp: Tensor, left: Tensor, right: Tensor, mask: Tensor = 
     right, Cr = _photo_image("right", right, u8, B, H, W, disp.device)
     if C != Cr:
         raise RuntimeError(f"photo_consistency: left has {C} channels and right {Cr}")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError("photo_consistency: mask must be a bool or uint8 tensor")
-        _check_u8("photo_consistency", mask.view(torch.uint8))
-        if tuple(mask.shape) != (B, H, W) or mask.device != disp.device:
-            raise RuntimeError(f"photo_consistency: mask must be ({B},{H},{W}) on the device of disp, got {tuple(mask.shape)}")
-        mask = mask.contiguous().view(torch.uint8)
+    mask = _mask_arg("photo_consistency", mask, B, H, W, disp.device, "disp")
     offs = [float(o) for o in row_offsets]
     if len(offs) > PHOTO_MAX_OFFSETS:
         raise RuntimeError(f"photo_consistency: {len(offs)} row offsets, at most {PHOTO_MAX_OFFSETS}")
     if want_dssim and not ssim:
         raise RuntimeError("photo_consistency: want_dssim needs ssim")
-    if not (disp.stride(2) == 1 and disp.stride(1) >= W and disp.stride(0) >= 0) and disp.numel():
-        disp = disp.contiguous()
+    disp = _row_dense(disp, W)
     lib = _lib.load()
     dev = disp.device
     R = len(offs)
@@ -1377,17 +1440,6 @@ def photo_consistency(disp: Tensor, left: Tensor, right: Tensor, mask: Tensor = 
 
 
 # ---------------------------------------------------------------- frames in, pictures out
-
-def _check_u8(name: str, *ts: Tensor):
-    """``_check`` for the uint8 tensors of the frame / picture ops (frames, LUT, side-by-side image)."""
-    for t in ts:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name}: expected tensors")
-        if not t.is_cuda:
-            raise RuntimeError(f"{name}: fsmi ops run on ROCm (HIP) device tensors only; got {t.device}")
-        if t.dtype != torch.uint8:
-            raise RuntimeError(f"{name}: expected uint8, got {t.dtype}")
-
 
 def frames_ingest(left: Tensor, right: Tensor, scale: float = 1.0, divis_by: int = 32, want_u8: bool = True):
     """scripts/run_demo.py:131-159 in one launch.  left, right: uint8 (B,H,W,C), C in {1,3,4} ->
@@ -1459,12 +1511,6 @@ def disp_metrics_blocks(H: int, W: int) -> int:
     return int(_lib.load().fsmi_disp_metrics_blocks(int(H), int(W)))
 
 
-def _u8_aligned(t: Tensor) -> Tensor:
-    """Contiguous and 4-byte aligned (the kernels read uint8 maps a word at a time)."""
-    t = t.contiguous()
-    return t if t.data_ptr() % 4 == 0 else t.clone()
-
-
 def disp_metrics(pred: Tensor, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.0), gt_scale: float = 1000.0,
                  want_error: bool = False):
     """train/utils.py:88-141 + train/losses.py:326-339 per pair, in two launches and without a host
@@ -1473,28 +1519,12 @@ def disp_metrics(pred: Tensor, gt: Tensor, mask: Tensor = None, thresholds=(1.0,
     (B,H,W); up to 8 thresholds -> (table (B,17) fp64, sums (B,17) fp64, error (B,H,W) fp32 or None).
     include/fsmi.h has the layout of the two rows and the arithmetic."""
     _check("disp_metrics", pred)
-    if not isinstance(gt, torch.Tensor):
-        raise TypeError("disp_metrics: expected tensors")
-    u8 = gt.dtype == torch.uint8
-    (_check_u8 if u8 else _check)("disp_metrics", gt)
     if pred.dim() != 3:
         raise RuntimeError(f"disp_metrics: pred must be (B,H,W), got {tuple(pred.shape)}")
     B, H, W = pred.shape
-    if tuple(gt.shape) != ((B, H, W, 3) if u8 else (B, H, W)) or gt.device != pred.device:
-        raise RuntimeError(f"disp_metrics: gt must be fp32 ({B},{H},{W}) or uint8 ({B},{H},{W},3) on the device of "
-                           f"pred, got {gt.dtype} {tuple(gt.shape)}")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError("disp_metrics: mask must be a bool or uint8 tensor")
-        _check_u8("disp_metrics", mask.view(torch.uint8))
-        if tuple(mask.shape) != (B, H, W) or mask.device != pred.device:
-            raise RuntimeError(f"disp_metrics: mask must be ({B},{H},{W}) on the device of pred, got {tuple(mask.shape)}")
-        mask = _u8_aligned(mask).view(torch.uint8)
-    thr = [float(t) for t in thresholds]
-    if len(thr) > METRICS_MAX_THRESHOLDS:
-        raise RuntimeError(f"disp_metrics: {len(thr)} thresholds, at most {METRICS_MAX_THRESHOLDS}")
-    if u8 and not float(gt_scale) > 0.0:
-        raise RuntimeError(f"disp_metrics: gt_scale = {gt_scale} must be positive")
+    u8 = _gt_arg("disp_metrics", gt, gt_scale, pred)
+    mask = _mask_arg("disp_metrics", mask, B, H, W, pred.device, "pred", align4=True)
+    thr, cthr = _thresholds_arg("disp_metrics", thresholds)
     lib = _lib.load()
     pred, gt = _c(pred), (_u8_aligned(gt) if u8 else _c(gt))
     dev = pred.device
@@ -1502,7 +1532,6 @@ def disp_metrics(pred: Tensor, gt: Tensor, mask: Tensor = None, thresholds=(1.0,
     sums = torch.empty((B, METRICS_NACC), device=dev, dtype=torch.float64)
     table = torch.empty((B, METRICS_NACC), device=dev, dtype=torch.float64)
     error = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_error else None
-    cthr = (ctypes.c_float * max(len(thr), 1))(*thr)        # rounded to fp32 here, compared in fp32
     _lib.check(lib.fsmi_disp_metrics(_p(pred), None if u8 else _p(gt), _p(gt) if u8 else None,
                                      _p(mask) if mask is not None else None, cthr, len(thr), float(gt_scale),
                                      _p(partials), _p(sums), _p(table), _p(error) if want_error else None, B, H, W,
@@ -1563,29 +1592,14 @@ def seq_metrics(preds, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.
     if not 1 <= R <= SEQ_MAX_ROWS:
         raise RuntimeError(f"seq_metrics: {R} rows, 1..{SEQ_MAX_ROWS}")
     _check("seq_metrics", *preds)
-    if not isinstance(gt, torch.Tensor):
-        raise TypeError("seq_metrics: expected tensors")
-    u8 = gt.dtype == torch.uint8
-    (_check_u8 if u8 else _check)("seq_metrics", gt)
-    if gt.dim() != (4 if u8 else 3) or (u8 and gt.shape[3] != 3):
-        raise RuntimeError(f"seq_metrics: gt must be fp32 (B,H,W) or uint8 (B,H,W,3), got {gt.dtype} {tuple(gt.shape)}")
+    u8 = _gt_arg("seq_metrics", gt, gt_scale)
     B, H, W = gt.shape[:3]
     dev = gt.device
     for r, p in enumerate(preds):
         if p.dim() != 3 or p.shape[0] != B or p.shape[1] < 1 or p.shape[2] < 1 or p.device != dev:
             raise RuntimeError(f"seq_metrics: row {r} must be ({B},h,w) on the device of gt, got {tuple(p.shape)}")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8):
-            raise RuntimeError("seq_metrics: mask must be a bool or uint8 tensor")
-        _check_u8("seq_metrics", mask.view(torch.uint8))
-        if tuple(mask.shape) != (B, H, W) or mask.device != dev:
-            raise RuntimeError(f"seq_metrics: mask must be ({B},{H},{W}) on the device of gt, got {tuple(mask.shape)}")
-        mask = mask.contiguous().view(torch.uint8)
-    thr = [float(t) for t in thresholds]
-    if len(thr) > METRICS_MAX_THRESHOLDS:
-        raise RuntimeError(f"seq_metrics: {len(thr)} thresholds, at most {METRICS_MAX_THRESHOLDS}")
-    if u8 and not float(gt_scale) > 0.0:
-        raise RuntimeError(f"seq_metrics: gt_scale = {gt_scale} must be positive")
+    mask = _mask_arg("seq_metrics", mask, B, H, W, dev, "gt")
+    thr, cthr = _thresholds_arg("seq_metrics", thresholds)
     if not float(beta) >= 0.0:
         raise RuntimeError(f"seq_metrics: beta = {beta} must not be negative")
     maxd = _per_row("seq_metrics", "max_disparity values", max_disparity, R, float("inf"))
@@ -1598,8 +1612,7 @@ def seq_metrics(preds, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.
         if not 0 <= int(r) < R:
             raise RuntimeError(f"seq_metrics: smooth row {r} of {R} rows")
         smooth[int(r)] = 1
-    # a view keeps its strides; a copy only where a line is not dense or runs backwards
-    preds = [p if p.stride(2) == 1 and p.stride(1) >= p.shape[2] and p.stride(0) >= 0 else p.contiguous() for p in preds]
+    preds = [_row_dense(p, p.shape[2]) for p in preds]
     gt = gt.contiguous()
     lib = _lib.load()
     NB = seq_metrics_blocks(H, W, R)
@@ -1609,7 +1622,6 @@ def seq_metrics(preds, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.
     loss = torch.empty((B,), device=dev, dtype=torch.float64)
     LL, CI, CF, CD = ctypes.c_longlong * R, ctypes.c_int * R, ctypes.c_float * R, ctypes.c_double * R
     rows, _keep = _lib.ptr_array([_p(p) for p in preds])
-    cthr = (ctypes.c_float * max(len(thr), 1))(*thr)        # rounded to fp32 here, compared in fp32
     _lib.check(lib.fsmi_seq_metrics(rows, LL(*[p.stride(0) for p in preds]), LL(*[p.stride(1) for p in preds]),
                                     CI(*[p.shape[1] for p in preds]), CI(*[p.shape[2] for p in preds]), CF(*mul),
                                     CF(*maxd), CD(*w), bytes(smooth), R, None if u8 else _p(gt), _p(gt) if u8 else None,

@@ -72,15 +72,7 @@ class RowProbe:
 
 
 def _disp(x: Tensor) -> Tensor:
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("photometric: disp must be a tensor")
-    if x.dim() == 2:
-        return x[None]
-    if x.dim() == 4 and x.shape[1] == 1:
-        return x[:, 0]
-    if x.dim() == 3:
-        return x
-    raise ValueError(f"photometric: disp must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(x.shape)}")
+    return ops._as_bhw(x, "photometric", "disp")
 
 
 def _image(x: Tensor, name: str) -> Tensor:
@@ -100,9 +92,7 @@ def _image(x: Tensor, name: str) -> Tensor:
 
 
 def _mask(mask):
-    if mask is None:
-        return None
-    return mask[None] if mask.dim() == 2 else mask[:, 0] if mask.dim() == 4 and mask.shape[1] == 1 else mask
+    return None if mask is None else ops._as_bhw(mask, "photometric", "mask")
 
 
 def consistency(disp: Tensor, left: Tensor, right: Tensor, mask: Optional[Tensor] = None, *, row_offsets=(),

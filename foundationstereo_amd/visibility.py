@@ -56,26 +56,14 @@ class Visibility:
         return self.counts.double() / float(self.classes.shape[1] * self.classes.shape[2])
 
 
-def _as_bhw(x: Tensor, name: str) -> Tensor:
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"visibility: {name} must be a tensor")
-    if x.dim() == 2:
-        return x[None]
-    if x.dim() == 4 and x.shape[1] == 1:
-        return x[:, 0]
-    if x.dim() == 3:
-        return x
-    raise ValueError(f"visibility: {name} must be (H,W), (B,H,W) or (B,1,H,W), got {tuple(x.shape)}")
-
-
 def classify(disp: Tensor, disp_right: Optional[Tensor] = None, *, occlusion: bool = True, occlusion_tol: float = 1.0,
              lr_thresh: float = 1.0, want_error: bool = False) -> Visibility:
     """One class per pixel of ``disp`` (fp32 (H,W), (B,H,W) or (B,1,H,W) on a HIP device).  ``disp_right``,
     the right view's disparity on the right image's grid (``right_disparity``), adds the left-right
     check; ``occlusion=False`` drops the z-buffer.  ``want_error`` (needs ``disp_right``) also returns
     the left-right difference.  Widths up to 8192.  Does not synchronise."""
-    d = _as_bhw(disp, "disp")
-    r = None if disp_right is None else _as_bhw(disp_right, "disp_right")
+    d = ops._as_bhw(disp, "visibility", "disp")
+    r = None if disp_right is None else ops._as_bhw(disp_right, "visibility", "disp_right")
     if want_error and r is None:
         raise ValueError("visibility.classify: want_error needs disp_right")
     classes, counts, error = ops.disp_visibility(d, r, occlusion_tol, lr_thresh, occlusion, want_error)
