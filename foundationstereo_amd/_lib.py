@@ -87,7 +87,6 @@ SIGNATURES = {
                          ctypes.POINTER(_I), ctypes.POINTER(_F), ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_double),
                          ctypes.c_char_p, _I, _P, _P, _P, ctypes.POINTER(_F), _I, ctypes.c_double, _F, _P, _P, _P, _P,
                          _I, _I, _I, _P],
-    "fsmi_debug_conv_timestamps": [_P],
     "fsmi_range_status": [_I, ctypes.POINTER(_I)],
     "fsmi_set_range_safe": [_I],
     "fsmi_range_poison": [_P, ctypes.c_longlong, _P],
@@ -144,8 +143,8 @@ def load():
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name, None)
-        if fn is None and (name.startswith("fsmi_debug_") or name == "fsmi_timer_dump_captured"):
-            continue                     # diagnostics absent from an older A/B build (FSMI_LIB)
+        if fn is None and name == "fsmi_timer_dump_captured":
+            continue                     # a diagnostic absent from an older A/B build (FSMI_LIB)
         if fn is None:
             raise FsmiError(f"{path}: missing symbol {name}")
         fn.argtypes = argtypes

@@ -31,7 +31,7 @@
 #include "conv_tiles.h"
 #include "fsmi_common.h"
 
-// activation range of the split.  Default (FSMI_HALO_RANGE 1):
+// activation range of the split:
 //   * 2D maps (mode 2): a block exponent fixed by the block's first 32-channel chunk with 8 bits
 //     of headroom, so every later chunk up to 2^9 x larger still fits fp16; a value beyond that
 //     sets the range flag (fsmi_range_status -> RangeError), never a silent inf.  Callers put the
@@ -40,28 +40,14 @@
 //   * NCDHW volumes (mode 1): the exact block max of every chunk with accumulator rescaling --
 //     a block's first chunk there is one depth plane, and planes differ by far more than 2^9
 //     (the bias-only w < d region of the cost volume).
-// Measured end to end (cfg2): mode 2 costs ~3 % against no scaling, mode 1 on every conv ~7 %;
-// volumes are ~10 % of the conv time.  FSMI_HALO_RANGE=0 builds an A/B variant without either
-// (fp16 range: |x| < 65504, 22 bits only for |x| >~ 0.1); 2 / 3 force mode 2 / 3 everywhere.
-#ifndef FSMI_HALO_RANGE
-#define FSMI_HALO_RANGE 1
-#endif
+// Measured end to end (cfg2): mode 2 costs ~3 % against no scaling (fp16 range: |x| < 65504, 22 bits
+// only for |x| >~ 0.1), mode 1 on every conv ~7 %; volumes are ~10 % of the conv time.
 template <bool D3>
-constexpr int range_mode() { return FSMI_HALO_RANGE == 1 ? (D3 ? 1 : 2) : FSMI_HALO_RANGE; }
+constexpr int range_mode() { return D3 ? 1 : 2; }
 // the wreg kernel's lambdas are forced inline: left to the inliner's cost model, clang outlines
 // the 128 x 8 x 32 volume tile's `segment` into a real call (captures passed through the stack,
 // 464 B of scratch) -- the build that faulted in round 1.  Measured neutral elsewhere.
-#ifndef FSMI_HALO_FORCE_INLINE
-#define FSMI_HALO_FORCE_INLINE 1
-#endif
-#if FSMI_HALO_FORCE_INLINE
 #define FSMI_HALO_INL __attribute__((always_inline))
-#else
-#define FSMI_HALO_INL
-#endif
-#ifndef FSMI_WREG_BPREF
-#define FSMI_WREG_BPREF 1                            // 0: A/B build, B fragments read just before their MFMAs
-#endif
 // MFMA products per MAC: 3 (default) = hi*hi + hi*lo + lo*hi, the ~22-bit split that keeps the
 // fp32 parity (|dd| < 1e-3 px); 1 = hi*hi only -- one fp16 product with fp32 accumulation, the
 // precision of the reference's own GPU path (fp16 autocast, scripts/run_demo.py:161).  The 1-product
@@ -71,9 +57,6 @@ constexpr int range_mode() { return FSMI_HALO_RANGE == 1 ? (D3 ? 1 : 2) : FSMI_H
 #define FSMI_NPROD 3
 #endif
 static_assert(FSMI_NPROD == 1 || FSMI_NPROD == 3, "FSMI_NPROD: 1 or 3 MFMA products per MAC");
-#ifndef FSMI_HALO_PERCOUT
-#define FSMI_HALO_PERCOUT 1                          // 0: A/B build reading one weight scale (row 0's)
-#endif
 
 namespace fsmi {
 namespace halo {
@@ -103,8 +86,6 @@ struct HaloArgs {
   int nrt, nct, npix, nco;         // row tiles, col tiles, pixel tiles (B*D*nrt*nct), cout tiles
   int nsplit, kpc;                 // split-K factor, (kd, channel chunk) pairs per split
   float* ws;                       // [nsplit][B][Cout][D*H*W] partial sums when nsplit > 1
-  unsigned long long* ts;          // debug (fsmi_debug_conv_timestamps): per-block wall-clock stamps
-  int dbg;                         // ablation (FSMI_CONV_DBG): 1 weights from one line, 2 no halo reloads
   // SelectiveConvGRU gate epilogues (act 3..5), core/update.py:83-95,117; all (B, gHd, H, W)
   // except gatt (B, 1, H, W)
   const float* gh;                 // hidden state h
@@ -172,9 +153,6 @@ constexpr int HROW = HKC + 8;      // padded LDS row (halves): conflict-free ds_
 // fp32 beyond 3.92).  Both halves are evaluated and one selected: the library erff branches on |z|,
 // and a GELU's inputs straddle |z| = 1 within every wave, so each wave ran both paths plus the
 // branch bookkeeping (~34 VALU per element vs ~25 here).
-#ifndef FSMI_GELU_FAST
-#define FSMI_GELU_FAST 1
-#endif
 __device__ __forceinline__ float erf_nb(float z) {
   const float t = z * z;
   float p = 7.847259258e-05f;
@@ -202,11 +180,7 @@ __device__ __forceinline__ float erf_nb(float z) {
   return fabsf(z) < 1.f ? small : big;
 }
 __device__ __forceinline__ float gelu_erf_h(float x) {
-#if FSMI_GELU_FAST
   return 0.5f * x * (1.f + erf_nb(x * 0.70710678118654752f));
-#else
-  return 0.5f * x * (1.f + erff(x * 0.70710678118654752f));
-#endif
 }
 __device__ __forceinline__ float sigm_h(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -227,7 +201,7 @@ __device__ __forceinline__ float sigm_h(float x) { return 1.f / (1.f + expf(-x))
 // loads (bias, residual, gate state) ahead of its stores.  Read through the HaloArgs fields
 // (which may alias the output) each load waited behind the previous element's store, and a
 // tile's epilogue paid one L2 round trip per element: 20-56 % of a block's lifetime on the
-// nsplit = 1 layers (tools/conv_phases.py).
+// nsplit = 1 layers (per-block phase stamps, round 3).
 template <bool RESPRE>
 __device__ __forceinline__ void store_el(const HaloArgs& a, float v, int co, int b, long long hw,
                                          float* __restrict__ out, const float2* __restrict__ sb,
@@ -283,7 +257,7 @@ __device__ __forceinline__ void store_out(const HaloArgs& a, float v, int co, in
 // Per-cout epilogue coefficients of one 16-row fragment (couts cb + (r&3) + 8(r>>2)): the
 // (2^-wexp * xinv, bias) pair and gamma.  Loaded once per cout block of a tile: fetched per
 // fragment they were a dependent L2/HBM round trip before each fragment's 16 stores -- 21-24 us of
-// a 170-200 us block on the nsplit = 1 loop layers (tools/conv_phases.py, round 3).
+// a 170-200 us block on the nsplit = 1 loop layers (per-block phase stamps, round 3).
 struct FragCoef {
   float2 q[16];
   float g[16];
@@ -307,7 +281,7 @@ __device__ __forceinline__ void frag_coef(const HaloArgs& a, float xinv, int cb,
 // fixed at compile time and one restrict scope: the fragment's residual / gate loads are issued
 // together, then 16 branch-free finishes and stores.  (The generic store_el per element compiled to
 // ~400 instructions per fragment with a wait per element: 20-56 % of a block's lifetime went to the
-// epilogue on the nsplit = 1 layers, tools/conv_phases.py.)
+// epilogue on the nsplit = 1 layers, per-block phase stamps of round 3.)
 template <int ACT, bool RESPRE>
 __device__ __forceinline__ void store_frag_c(const HaloArgs& a, const f32x16& v, const FragCoef& c, int cb, int b,
                                              long long hw, int hw2, float* __restrict__ out,
@@ -469,14 +443,7 @@ __device__ __forceinline__ void store4(const HaloArgs& a, const float (&v)[4], i
 // chan() returns a GLOBAL (address space 1) pointer: a pointer rebuilt from an integer is generic,
 // and loads through it were flat_load_dword -- which count in lgkmcnt as well as vmcnt, so every
 // LDS operand wait after a chunk's halo loads also waited for those HBM loads (round 5).
-#ifndef FSMI_HALO_FLAT
-#define FSMI_HALO_FLAT 0                             // 1: the round-4 generic pointers (A/B build only)
-#endif
-#if FSMI_HALO_FLAT
-typedef const float* gcfptr;
-#else
 typedef const __attribute__((address_space(1))) float* gcfptr;
-#endif
 
 struct SegBases {
   uintptr_t p[kHMaxSeg];
@@ -500,17 +467,13 @@ struct SegBases {
 // Input-halo staging for a TR x 32 pixel tile: task = (halo pixel, 8-channel
 // group); per task a packed descriptor (clamped pixel offset << 3 | in-image << 2
 // | group) computed once per block; a chunk is loaded into registers one chunk
-// ahead and split into fp16 hi/lo when stored to LDS.
-// DEFER: keep the raw loads and mask them where they are read (absmax / store), so the loads stay in
-// flight until then; otherwise they are masked on arrival -- which the compiler schedules right after
-// the loads, waiting on them there (the default, kept for the tuned tiles' register budgets).
-template <int KS, int TR, int STR = 1, bool DEFER = false>
+// ahead, masked on arrival, and split into fp16 hi/lo when stored to LDS.
+template <int KS, int TR, int STR = 1>
 struct HaloStage {
   // STR = 2: a stride-2 conv's window, (2 TR + 1) x 65 input pixels for TR x 32 outputs
   static constexpr int PD = KS / 2, HR = STR * (TR - 1) + KS, HC = STR * 31 + KS, NHP = HR * HC;
   static constexpr int X_TASKS = NHP * (HKC / 8), X_PER_T = (X_TASKS + 255) / 256;
   int desc[X_PER_T];
-  int lim[DEFER ? X_PER_T : 1];    // DEFER: channels of task u's group that hold data (0 outside)
   f32x8 xv[X_PER_T];
 
   __device__ __forceinline__ void init(const HaloArgs& a, int tid, int r0, int c0) {
@@ -546,41 +509,20 @@ struct HaloStage {
       // over constant indices, so the kernarg arrays are never indexed per lane
       const gcfptr src = seg.chan(a, cic, HW) + poff + pix;
       const bool ok = (desc[u] & 4) && plane_ok;
-      if constexpr (DEFER) {
-        // one input segment of < 4 GB per batch item (the launcher checks): byte offsets from the
-        // block-uniform base, channel j of the group at ob0 + j * HW * 4, clamped to the group's last
-        // channel with one min (offsets grow with j) -- two VALU per load instead of a 64-bit product
+      f32x8 v;
+      if (full) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = src[static_cast<size_t>(j) * HW];
+      } else {
         const int nv = a.Cin - ci0;                // may be <= 0 in the padded tail
-        const int last = max(0, min(nv, 8) - 1);
-        const unsigned hwb = static_cast<unsigned>(HW) * 4u;
-        const unsigned ob0 = (static_cast<unsigned>(cic) * static_cast<unsigned>(HW) +
-                              static_cast<unsigned>(poff) + static_cast<unsigned>(pix)) * 4u;
-        const unsigned oblast = ob0 + static_cast<unsigned>(last) * hwb;
-        using gccptr = const __attribute__((address_space(1))) char*;
-        const gccptr base = reinterpret_cast<gccptr>(seg.p[0]);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const unsigned ob = full ? ob0 + j * hwb : min(ob0 + j * hwb, oblast);
-          xv[u][j] = *reinterpret_cast<gcfptr>(base + ob);
+          const float t = src[static_cast<size_t>(max(0, min(j, nv - 1))) * HW];
+          v[j] = j < nv ? t : 0.f;
         }
-        lim[u] = ok ? (full ? 8 : max(0, min(nv, 8))) : 0;
-        (void)src;
-      } else {
-        f32x8 v;
-        if (full) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = src[static_cast<size_t>(j) * HW];
-        } else {
-          const int nv = a.Cin - ci0;              // may be <= 0 in the padded tail
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float t = src[static_cast<size_t>(max(0, min(j, nv - 1))) * HW];
-            v[j] = j < nv ? t : 0.f;
-          }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xv[u][j] = ok ? v[j] : 0.f;
       }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) xv[u][j] = ok ? v[j] : 0.f;
     }
   }
 
@@ -591,7 +533,7 @@ struct HaloStage {
 #pragma unroll
     for (int u = 0; u < X_PER_T; ++u)
 #pragma unroll
-      for (int j = 0; j < 8; ++j) m = fmaxf(m, !DEFER || j < lim[DEFER ? u : 0] ? fabsf(xv[u][j]) : 0.f);
+      for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(xv[u][j]));
     return m;
   }
 
@@ -607,7 +549,7 @@ struct HaloStage {
         const int hp = task % NHP, g = task / NHP;
         f32x8 x;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = !DEFER || j < lim[DEFER ? u : 0] ? xv[u][j] * scale : 0.f;
+        for (int j = 0; j < 8; ++j) x[j] = xv[u][j] * scale;
         if constexpr (RMODE == 2) {               // largest scaled |x| of the task, one compare after
           float m = 0.f;
 #pragma unroll
@@ -688,20 +630,7 @@ __device__ __forceinline__ void flag_overflow(const HaloArgs& a, bool ovf) {
   if (ovf && a.ovf) *a.ovf = 1;    // vector store from the lanes that saw one (same value, benign race)
 }
 
-constexpr int kHeadroom3 = 4;
 constexpr int kHeadroom1 = 4;       // mode 1: exponent re-aimed 4 bits below a chunk's fit
-
-// mode 3: does any lane's chunk value overflow fp16 at scale 2^sx?  One flag word per wave.
-__device__ __forceinline__ void range3_check(int* rflag, float local_max, int sx, int lane, int wave) {
-  const bool need = local_max * exp2i(sx == kNoExp ? 0 : sx) >= 32768.f;
-  const unsigned long long any = __builtin_amdgcn_ballot_w64(need);
-  if (lane == 0) rflag[wave] = any != 0ull;
-}
-
-__device__ __forceinline__ bool range3_any(const int* rflag) {
-  const int4 f = *reinterpret_cast<const int4*>(rflag);
-  return (f.x | f.y | f.z | f.w) != 0;
-}
 
 __device__ __forceinline__ float red4_max(const float* red) {
   const float4 r = *reinterpret_cast<const float4*>(red);       // one ds_read_b128
@@ -773,7 +702,7 @@ __device__ __forceinline__ void mma3(f32x16 (&acc)[TM][TN], const half8 (&ah)[TM
 // global loads hidden under the main loop): lsb[c] = (2^-wexp, bias) and lg[c] = gamma of cout
 // m0 + c (clamped to Cout - 1).  Fetched from global memory per fragment in the epilogue they were a
 // dependent L2/HBM round trip before each fragment's 16 stores -- 21-24 us of a 170-200 us block on
-// the nsplit = 1 loop layers (tools/conv_phases.py, round 3); from LDS each is ~100 cycles, and one
+// the nsplit = 1 loop layers (per-block phase stamps, round 3); from LDS each is ~100 cycles, and one
 // fragment's coefficients at a time keep the register peak of the per-fragment loads.
 template <int BM>
 struct EpiCoef {
@@ -884,7 +813,6 @@ __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
   __shared__ __attribute__((aligned(16))) _Float16 Wh[2][BM][HROW];
   __shared__ __attribute__((aligned(16))) _Float16 Wl[2][BM][HROW];
   __shared__ __attribute__((aligned(16))) float red[4];   // per-wave chunk max |x| (block exponent)
-  __shared__ __attribute__((aligned(16))) int rflag[4];   // per-wave 'chunk overflows the exponent' (mode 3)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave % WM, wn = wave / WM;
@@ -956,37 +884,12 @@ __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
   bool ovf = false;
   constexpr bool m1 = RM == 1;     // per-chunk exponent (mode 1)
   for (int cc = cc_begin; cc < cc_end; ++cc) {
-    if constexpr (RM == 3) {
-      const float lm = hs.absmax();
-      if (cc == cc_begin) {
-        const float m = wave_max(lm);
-        if (lane == 0) red[wave] = m;
-      } else {
-        range3_check(rflag, lm, sx, lane, wave);
-      }
-    } else if (m1 || (RM == 2 && sx == kNoExp)) {
+    if (m1 || (RM == 2 && sx == kNoExp)) {
       const float m = wave_max(hs.absmax());
       if (lane == 0) red[wave] = m;           // m is wave-uniform (SGPR)
     }
     __syncthreads();               // every wave is done with the previous chunk's halo; maxima visible
-    if constexpr (RM == 3) {
-      if (cc == cc_begin) {
-        const float bm = red4_max(red);
-        ovf |= !(bm <= 3.4e38f);
-        sx = bm > 0.f ? __builtin_amdgcn_readfirstlane(chunk_exp<kHeadroom3>(bm)) : 0;
-      } else if (__builtin_amdgcn_readfirstlane(range3_any(rflag))) {   // rare: beyond the headroom
-        const float m = wave_max(hs.absmax());
-        if (lane == 0) red[wave] = m;
-        __syncthreads();
-        const float bm = red4_max(red);
-        ovf |= !(bm <= 3.4e38f);
-        const int se = __builtin_amdgcn_readfirstlane(chunk_exp<kHeadroom3>(bm));
-        if (se < sx) {
-          rescale_acc<TM, TN>(acc, exp2i(se - sx));
-          sx = se;
-        }
-      }
-    } else if (m1) {
+    if (m1) {
       const float bm = red4_max(red);
       ovf |= !(bm <= 3.4e38f);                  // an inf input (NaN is ignored by the max)
       // rescale only when the chunk does not fit the current exponent; then re-aim with headroom
@@ -1070,8 +973,6 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
   const int hsel = lane >> 5, rl = lane & 31;
   const int nck = a.CinP / HKC;
   const int nq = D3 ? a.KD * nck : nck;            // chunks = (kd, 32-channel chunk) pairs, kd major
-  unsigned long long* tsb = a.ts ? a.ts + static_cast<size_t>(blockIdx.x) * 40 : nullptr;
-  if (tsb && threadIdx.x == 0) tsb[0] = wall_clock64();
 
   // one segment: chunks [cc_begin, cc_end) of tile tc (group g: cc_begin + g, + g + KG, ...);
   // partial: raw sums into ws slot tc.split
@@ -1084,9 +985,8 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
     half8 wf[2][TM][2][2];         // [buffer][i][k half][hi, lo]
     auto load_wf = [&](auto buf_c, int cc, int tap) FSMI_HALO_INL {
       constexpr int buf = decltype(buf_c)::value;
-      size_t base = D3 ? (static_cast<size_t>((cc / nck) * NTAP + tap) * nck + cc % nck) * a.CoutP * HKC
-                       : (static_cast<size_t>(tap) * nck + cc) * a.CoutP * HKC;
-      if (a.dbg & 1) base = 0;
+      const size_t base = D3 ? (static_cast<size_t>((cc / nck) * NTAP + tap) * nck + cc % nck) * a.CoutP * HKC
+                             : (static_cast<size_t>(tap) * nck + cc) * a.CoutP * HKC;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1130,7 +1030,7 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
           bl[S & 1][j] = *reinterpret_cast<const half8*>(&gXl[hp][16 * k + 8 * hsel]);
         }
       };
-      if constexpr (FSMI_WREG_BPREF) read_b(std::integral_constant<int, 0>());
+      read_b(std::integral_constant<int, 0>());
       static_for<0, NTAP>([&](auto tap_c) FSMI_HALO_INL {
         constexpr int tap = decltype(tap_c)::value;
         constexpr bool last = tap + 1 == NTAP;
@@ -1145,11 +1045,7 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         static_for<0, 2>([&](auto k_c) FSMI_HALO_INL {
           constexpr int k = decltype(k_c)::value, S = 2 * tap + k;
-          if constexpr (FSMI_WREG_BPREF) {
-            if constexpr (S + 1 < 2 * NTAP) read_b(std::integral_constant<int, S + 1>());   // next step's B
-          } else {
-            read_b(std::integral_constant<int, S>());   // A/B: this step's B, read just before its MFMAs
-          }
+          if constexpr (S + 1 < 2 * NTAP) read_b(std::integral_constant<int, S + 1>());   // next step's B
           half8 ah[TM], al[TM];
 #pragma unroll
           for (int i = 0; i < TM; ++i) {
@@ -1178,7 +1074,6 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
         if (lane == 0) gred[wave] = m;          // m is wave-uniform (SGPR)
       }
       __syncthreads();             // every wave is done with the previous chunk's halo; maxima visible
-      if (tsb && threadIdx.x == 0 && q < 36) tsb[1 + q] = wall_clock64();
       if (valid) {
         if (m1) {
           const float bm = red4_max(gred);
@@ -1193,7 +1088,7 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
           sx = __builtin_amdgcn_readfirstlane(chunk_exp<kRangeHeadroom>(red4_max(gred)));
         }
         hs.template store<RM>(gXh, gXl, tid, exp2i(sx == kNoExp ? 0 : sx), ovf);
-        if (cc + KG < cc_end && !(a.dbg & 2)) {
+        if (cc + KG < cc_end) {
           if constexpr (D3) hs.load(a, tc.b, (cc + KG) % nck, STR * tc.d0 + (cc + KG) / nck - a.PDD + a.sd);
           else hs.load(a, tc.b, cc + KG);
         }   // in flight during this chunk's taps
@@ -1218,7 +1113,6 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
       stage(q);
       if (q < n_g) chunk(std::integral_constant<int, 0>(), c_first + KG * q);
     }
-    if (tsb && threadIdx.x == 0) tsb[37] = wall_clock64();
     flag_overflow(a, ovf);
     float xinv = exp2i(sx == kNoExp ? 0 : -sx);
     unsigned fown = ~0u;
@@ -1256,10 +1150,6 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
       xinv = 1.f;
     }
     conv_epilogue<TM, TN, D3, D3 || KS == 2>(a, acc, xinv, tc, wm, wn, lane, partial, ecoef.sb, ecoef.g, fown);
-    if (tsb && threadIdx.x == 0) {
-      tsb[38] = wall_clock64();
-      tsb[39] = (static_cast<unsigned long long>(cc_end - cc_begin) << 32) | blockIdx.x;
-    }
   };
 
   unsigned bid = blockIdx.x, nb = gridDim.x;
@@ -1315,7 +1205,7 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
   constexpr int STAGE_TAP = NTAP > 1 ? 1 : 0;      // the tap whose MFMAs cover the next chunk's store
   using HS = HaloStage<KS, TR>;
   constexpr int RM = range_mode<false>();
-  static_assert(RM == 2 || RM == 0, "pipelined tiles: range mode 2 (or none)");
+  static_assert(RM == 2, "pipelined tiles: range mode 2");
   __shared__ __attribute__((aligned(16))) _Float16 Xh[2][HS::NHP][HROW];
   __shared__ __attribute__((aligned(16))) _Float16 Xl[2][HS::NHP][HROW];
   __shared__ __attribute__((aligned(16))) float red[4];
@@ -1358,7 +1248,7 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
 
   int sx = kNoExp;
   bool ovf = false;
-  auto scale = [&]() FSMI_HALO_INL { return RM == 2 ? exp2i(sx == kNoExp ? 0 : sx) : 1.f; };
+  auto scale = [&]() FSMI_HALO_INL { return exp2i(sx == kNoExp ? 0 : sx); };
   auto fix_exponent = [&]() FSMI_HALO_INL {        // block-wide max of the registers' chunk -> sx
     const float m = wave_max(hs.absmax());
     if (lane == 0) red[wave] = m;
@@ -1368,7 +1258,7 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
   // prologue: chunk 0 -> buffer 0 (its max fixes the exponent), chunk 1 into registers
   load_wf(std::integral_constant<int, 0>(), c_first, 0);
   hs.load(a, tc.b, c_first);
-  if (RM == 2) fix_exponent();
+  fix_exponent();
   hs.template store<RM>(Xh[0], Xl[0], tid, scale(), ovf);
   if (n > 1) hs.load(a, tc.b, c_first + 1);
   __syncthreads();
@@ -1405,7 +1295,7 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
       if (tap == STAGE_TAP && q + 1 < n) {
         // next chunk: registers (loaded one chunk ago) -> fp16 hi / lo -> the other buffer, then the
         // chunk after it into the registers
-        if (RM == 2 && sx == kNoExp) fix_exponent();   // every chunk so far all zero (uniform)
+        if (sx == kNoExp) fix_exponent();   // every chunk so far all zero (uniform)
         hs.template store<RM>(Xh[P ^ 1], Xl[P ^ 1], tid, scale(), ovf);
         if (q + 2 < n) hs.load(a, tc.b, cc + 2);
         __builtin_amdgcn_sched_barrier(0);
@@ -1433,7 +1323,7 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
   }
   if (q < n) chunk(std::integral_constant<int, 0>(), q);
   flag_overflow(a, ovf);
-  conv_epilogue<TM, TN, false>(a, acc, exp2i(sx == kNoExp || RM != 2 ? 0 : -sx), tc, wm, wn, lane, a.nsplit > 1,
+  conv_epilogue<TM, TN, false>(a, acc, exp2i(sx == kNoExp ? 0 : -sx), tc, wm, wn, lane, a.nsplit > 1,
                                 ecoef.sb, ecoef.g);
 }
 

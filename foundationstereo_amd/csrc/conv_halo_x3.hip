@@ -89,9 +89,6 @@ void split_reduce(const HaloArgs& a_in, hipStream_t s) {
 
 using namespace fsmi;
 
-// debug phase stamps (fsmi_debug_conv_timestamps): halo convs here, the EdgeNeXt MLP kernel too
-unsigned long long* g_conv_ts = nullptr;
-
 namespace {
 
 // launches per tile config as launched, indexed by halo::encode_cfg (conv_tiles.h): fsmi_conv_launch_counts
@@ -181,7 +178,6 @@ int run_halo(HaloArgs& a, const char* what, const float* const* seg_ptr, const i
     a.nsplit = 1;
     a.kpc = KD * a.CinP / HKC;
     a.ws = nullptr;
-    a.ts = nullptr;
     a.ovf = range_flag_device();
     g_cfg_launches[encode_cfg(tc)].fetch_add(1, std::memory_order_relaxed);
     const int rc = launch_depth(a, s);
@@ -234,27 +230,13 @@ int run_halo(HaloArgs& a, const char* what, const float* const* seg_ptr, const i
   nsplit = max(1, min(nsplit, nck));
   // in-block K groups (conv_halo.h, KG = 2; 16 + c = tile c with K groups): the block's two
   // wave groups split its chunks and sum through LDS -- no partials in memory, no reduce pass.
-  // FSMI_HALO_KG=2 (A/B) turns every eligible split-K >= 2 into K groups + half the splits.
-  static const int kg_env = [] {
-    const char* e = std::getenv("FSMI_HALO_KG");
-    return e ? std::atoi(e) : -1;
-  }();
-  if (tc.kg == 1 && kg_env == 2 && tile_in(tc.id, kTileKG) && nsplit >= 2) {   // A/B: fold 2 splits
-    tc.kg = 2;
-    nsplit = (nsplit + 1) / 2;
-  }
+  // They run only where the cfg asks for them; a split-K factor is never turned into K groups.
   a.kpc = (nck + nsplit - 1) / nsplit;
   a.nsplit = (nck + a.kpc - 1) / a.kpc;                    // no empty splits
   FSMI_CHECK_ARG(a.nsplit == 1 || (ws && per_split * a.nsplit <= ws_floats),
                  "%s: split-K %d needs %lld workspace floats", what, a.nsplit, per_split * a.nsplit);
   a.ws = ws;
-  a.ts = g_conv_ts;
   a.ovf = range_flag_device();
-  static const int conv_dbg = [] {
-    const char* e = std::getenv("FSMI_CONV_DBG");
-    return e ? std::atoi(e) : 0;
-  }();
-  a.dbg = conv_dbg;
   g_cfg_launches[encode_cfg(tc)].fetch_add(1, std::memory_order_relaxed);
   a.clk = conv_clock(a, s, encode_cfg(tc), KS, KD,
                      4ll * tc.kg * a.npix * a.nco * a.nsplit * (a.up == 2 ? 8 : a.up == 4 ? 4 : 1));
@@ -272,19 +254,11 @@ int run_halo(HaloArgs& a, const char* what, const float* const* seg_ptr, const i
 
 }  // namespace
 
-// Debug: while buf is non-NULL every halo conv launch records, per block, thread 0's wall clock
-// (100 MHz) at start [0], at each chunk's staging barrier [1..36], before / after the epilogue
-// [37] / [38] and (chunks << 32 | block) [39] into buf[block * 40 ..] (tools/conv_phases.py).
 extern "C" int fsmi_conv_launch_counts(long long* counts, int n, int reset) {
   FSMI_CHECK_ARG(counts && n > 0 && n <= 64, "fsmi_conv_launch_counts: 1..64 counters");
   for (int i = 0; i < n; ++i) counts[i] = g_cfg_launches[i].load(std::memory_order_relaxed);
   if (reset)
     for (auto& c : g_cfg_launches) c.store(0, std::memory_order_relaxed);
-  return FSMI_OK;
-}
-
-extern "C" int fsmi_debug_conv_timestamps(unsigned long long* buf) {
-  g_conv_ts = buf;
   return FSMI_OK;
 }
 
@@ -359,12 +333,8 @@ extern "C" int fsmi_conv3d_halo_x3_ex(const float* x, int Cin, const void* whi, 
   a.res_pre = res_pre;
   a.res_bstride = static_cast<long long>(Cout) * D * H * W;
   // (17, 1, 1) disparity-axis convs (Conv3dNormActReduced.conv2) on the depth-blocked tile unless a
-  // tile is forced; FSMI_DEPTH_TILE=0 keeps the generic volume tiles (A/B)
-  static const bool depth_tile = [] {
-    const char* e = std::getenv("FSMI_DEPTH_TILE");
-    return !e || std::atoi(e) != 0;
-  }();
-  if (stride == 1 && KS == 1 && KD == 17 && cfg < 0 && depth_tile) cfg = 30;
+  // tile is forced (conv_out at cfg2: 429 us on the generic volume tile, 338 us on this one)
+  if (stride == 1 && KS == 1 && KD == 17 && cfg < 0) cfg = 30;
   const float* seg[1] = {x};
   const int ch[1] = {Cin}, tot[1] = {Cin};
   return run_halo(a, "fsmi_conv3d_halo_x3", seg, ch, tot, 1, whi, wlo, scale_bias, out, Cout, 0, B, Cout, KS, H, W,

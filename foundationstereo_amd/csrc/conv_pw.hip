@@ -19,9 +19,6 @@
 // Entry: run_halo (conv_halo_x3.hip) with a pointwise cfg; KS = 1, 2D, H*W % 4 == 0, 16-B aligned segments.
 #include "conv_halo.h"
 
-#ifndef FSMI_PW_TWOBAR
-#define FSMI_PW_TWOBAR 0                           // 1: the round-2 schedule (a second barrier per chunk)
-#endif
 #ifndef FSMI_PW_WLD_ADJ
 #define FSMI_PW_WLD_ADJ 0
 #endif
@@ -151,8 +148,10 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
   float scale = 1.f;
   int sx = kNoExp;
   bool ovf = false;
-  // chunk q (buffer parity P): prefetch weights q+1 and chunk q+NS-1, wait for chunk q and
-  // weights q (the 2*OPS + WLD younger memory ops may stay in flight), barrier, MFMAs, barrier.
+  // chunk q (buffer parity P): prefetch weights q+1, wait for chunk q and weights q (the
+  // (NS-2)*OPS + WLD younger memory ops may stay in flight), barrier, refill the slot of chunk q-1
+  // with chunk q+NS-1, MFMAs.  (A second barrier per chunk after the MFMAs, the round-2 schedule,
+  // measured neutral against this one: 52.6 vs 53.2 us on gru04.zr_s)
   // LAST (the odd tail step, q = n - 1): its weight prefetch would be dead code -- the compiler
   // drops it -- so it issues none and its wait counts none.  The n == 1 tail follows the prologue
   // directly, with only the (NS - 2) clamped DMA groups after chunk 0's; the static check
@@ -163,18 +162,12 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
     constexpr int W = LAST ? 0 : WLD;
     const int c = c_begin + q;
     if constexpr (!LAST) load_wf(std::integral_constant<int, P ^ 1>(), min(c + 1, c_end - 1));
-#if FSMI_PW_TWOBAR
-    dma(min(c + NS - 1, c_end - 1), (q + NS - 1) % NS);
-    wait_vmcnt<2 * OPS + W>();                     // this wave's part of chunk q has landed
-    bar();                                         // ... and every wave's
-#else
     // one barrier per chunk: chunk q's DMA is waited for (chunks q+1 .. q+NS-2 and the weights just
     // issued may stay in flight), the barrier makes every wave's part visible AND retires every
     // wave's reads of chunk q-1's slot, which chunk q+NS-1 then refills
     wait_vmcnt<(NS - 2) * OPS + W>();
     bar();
     dma(min(c + NS - 1, c_end - 1), (q + NS - 1) % NS);
-#endif
     const float* xs = ring[q % NS];
     // block exponent (range mode 2) from the first chunk holding a nonzero value (an all-zero first
     // chunk would leave scale 1 and drop small later values to fp16 subnormals)
@@ -255,10 +248,6 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
       }
       mma3<TM, TN>(acc, ah, al, bh, bl);
     }
-#if FSMI_PW_TWOBAR
-    wait_lgkm0();
-    bar();                                         // every wave is done with slot q % NS
-#endif
   };
   // prologue: weights of the first chunk, then NS - 1 chunks in flight; the chunk loop sits inside
   // the same branch, so every path to a ring wait passes the prologue's DMAs

@@ -222,8 +222,8 @@ __global__ __launch_bounds__(kThreads) void stem_stream_kernel(const float* __re
 // (A / Bm = the proj_cmb halves of the concat volume folded through the stem weight, bias in A).
 //
 // Block = (b, h, WT = 4*WQ column tile, DCH = 4*DQN disparity chunk); thread = 4 d x 4 w, so a
-// wave-instruction store covers 4 rows of 256 contiguous bytes.  Measured per-block timeline
-// (tools/build_phases.py) drove the structure: every block runs at once (~1 wave per SIMD at
+// wave-instruction store covers 4 rows of 256 contiguous bytes.  A measured per-block timeline
+// (round 3) drove the structure: every block runs at once (~1 wave per SIMD at
 // cfg2), so each dependent global round trip costs ~3 us and the volume stores, all issued in one
 // phase, run at the chip's write rate (~7 TB/s); the kernel is therefore
 //   1. ONE staging round trip: the fl rows (WT columns), the fr rows (the WT + DCH columns the
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
                                                               const float* __restrict__ Bm,
                                                               const float* __restrict__ Wg,
                                                               float* __restrict__ out, int C, int Cs, int D,
-                                                              int H, int W, int WQ, int DQN, int nwt, int ndc, int dbg,
+                                                              int H, int W, int WQ, int DQN, int nwt, int ndc,
                                                               unsigned long long* clk) {
   constexpr int G = kBuildG, NPH = G / GP;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -328,10 +328,6 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
   // output (i, j) (d = d0+4dq+i, w = w0+4wq+j) uses position base + j - i = window slot j - i + 4
   const int base = 4 * (wq - dq) + DCH;
   const int wl0 = w0 + 4 * wq, dl0 = d0 + 4 * dq;
-  // dbg bit 2: per-block phase timestamps (wall clock, 100 MHz) of thread 0 into output channel 0
-  unsigned long long* ts = reinterpret_cast<unsigned long long*>(out) + static_cast<size_t>(blockIdx.x) * 16;
-  const bool tsr = (dbg & 4) && tid == 0;
-  if (tsr) ts[0] = wall_clock64();
 
   // epilogue operands travel with the first phase
   build_stage_rows<VEC>(A + static_cast<size_t>(b) * Cs * plane + static_cast<size_t>(h) * W, plane, Cs, WT, w0, W,
@@ -344,7 +340,7 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
   const size_t oplane = static_cast<size_t>(D) * plane;
   float* dst = out + static_cast<size_t>(b) * Cs * oplane + static_cast<size_t>(dl0) * plane +
                static_cast<size_t>(h) * W + wl0;
-  const bool wok = wl0 < W && !(dbg & 2);          // dbg bit 1: skip the stores (compute timing)
+  const bool wok = wl0 < W;
 
   // dot products of the thread's 4 d x 4 w outputs for groups [g0, g0 + GP) (staged at slots
   // 0..GP-1).  Output (i, j) is l_j * r_k, k = j - i + 4 (R window slot).  v_pk_fma_f32 takes
@@ -361,7 +357,6 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
       const float* R = Rg + gl * Cg * RS + base;
       f2 q10 = 0.f, q20 = 0.f, q00 = 0.f, q12 = 0.f, q22 = 0.f, q02 = 0.f;
       float s01 = 0.f, s30 = 0.f, s03 = 0.f, s32 = 0.f;
-      const int cend = (dbg & 1) ? 0 : Cg;       // dbg bit 0: skip the dot products (store-path timing)
       auto step = [&](const f4& l, const f4& ra, const f4& rb) {   // ra: slots 0..3, rb: 4..7
         const f2 l01 = l.xy, l23 = l.zw;
         q10 += l01 * ra.ww;                        // (1,0) (2,1)  r3
@@ -379,7 +374,7 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
       // channels 4 at a time, all 12 LDS reads issued before the FMAs (the asm FMAs block the
       // compiler's own unrolling); the channel order of every sum is unchanged
       int c = 0;
-      for (; c + 4 <= cend; c += 4, L += 4 * WT, R += 4 * RS) {
+      for (; c + 4 <= Cg; c += 4, L += 4 * WT, R += 4 * RS) {
         f4 l[4], ra[4], rb[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -390,7 +385,7 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
 #pragma unroll
         for (int u = 0; u < 4; ++u) step(l[u], ra[u], rb[u]);
       }
-      for (; c < cend; ++c, L += WT, R += RS)
+      for (; c < Cg; ++c, L += WT, R += RS)
         step(*reinterpret_cast<const f4*>(L), *reinterpret_cast<const f4*>(R - 4), *reinterpret_cast<const f4*>(R));
       float (&o)[4][4] = gwc[g0 + gl];
       o[1][0] = q10.x; o[2][1] = q10.y; o[2][0] = q20.x; o[3][1] = q20.y;
@@ -442,13 +437,10 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
     build_stage_rows<VEC>(frb + static_cast<size_t>(ph) * GP * Cg * plane, plane, GP * Cg, RS, rs0, W, Rg, tid, nthr);
     __builtin_amdgcn_s_waitcnt(0);                 // this thread's LDS-DMA pieces have landed
     __syncthreads();
-    if (tsr) ts[1 + 2 * ph] = wall_clock64();
     norms(ph * GP);
     if (active) dots(ph * GP);
-    if (tsr) ts[2 + 2 * ph] = wall_clock64();
   }
   __syncthreads();                                 // invn complete
-  if (tsr) ts[9] = wall_clock64();
   if (!active) return;
   // normalise: gwc *= inv|L|[w] * inv|R|[w - d]
 #pragma unroll
@@ -482,7 +474,7 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
         for (int g = 0; g < G; ++g) sacc += wv[g] * gwc[g][i][j];
         v[j] = av[j] + bv[j - i + 4] + sacc;       // Bm staged as 0 left of column 0: the w < d zeros
       }
-      if (dl0 + i < D && wok && !((dbg & 4) && o == 0)) {   // dbg 4: channel 0 holds the timestamps
+      if (dl0 + i < D && wok) {
         float* pp = po + static_cast<size_t>(i) * plane;
         if constexpr (VEC == 4) {
           *reinterpret_cast<float4*>(pp) = make_float4(v[0], v[1], v[2], v[3]);
@@ -493,11 +485,6 @@ __global__ __launch_bounds__(kThreads) void build_stem_kernel(const float* __res
         }
       }
     }
-  }
-  if (tsr) {
-    ts[10] = wall_clock64();
-    __builtin_amdgcn_s_waitcnt(0);
-    ts[11] = wall_clock64();
   }
   clock_end(clk);
 }
@@ -598,8 +585,9 @@ int launch_gwc(const float* fl, const float* fr, float* out, int B, int C, int G
 // Single-pass build tile: thread grid WQ column quads x DQN disparity quads (<= 256 threads, one
 // block per CU -- the LDS image is ~130 KB at cfg2 -- so the default aims for at most one block
 // per CU and few column tiles).  Groups are staged in the fewest phases whose LDS image fits the
-// CU's 160 KB.  FSMI_BUILD_TILE = "WQ,DQN" overrides (A/B measurement); FSMI_BUILD_DBG: 1 no dot
-// products, 2 no stores, 4 phase timestamps (tools/build_phases.py).
+// CU's 160 KB.  FSMI_BUILD_TILE = "WQ,DQN" overrides the tile: tests/test_gpu_parity.py's
+// test_build_stem_tiles reaches the ragged tiles through it, and every value it accepts computes
+// the right volume (the tile only sets how the output is divided among blocks and threads).
 int launch_build_stem(const float* fl, const float* fr, const float* A, const float* Bm, const float* Wg, float* out,
                       int B, int C, int Cs, int D, int H, int W, hipStream_t s) {
   const int Cg = C / kBuildG;
@@ -627,14 +615,8 @@ int launch_build_stem(const float* fl, const float* fr, const float* A, const fl
   // products -- cfg3 (4 pairs, 960 tiles): 0.40 -> 0.47-0.48 of HBM peak, while cfg2 at 80 KB loses
   // 0.49 -> 0.45.  (A persistent variant -- one block per CU walking its tiles and prefetching the
   // next tile by LDS-DMA during the current stores -- gained only 0.395 -> 0.402 at cfg3; dropped.)
-  // FSMI_BUILD_LDS_KB overrides the budget (A/B).
   const int nwt0 = (W + WT - 1) / WT, ndc0 = (D + DCH - 1) / DCH;
-  static const int lds_env = [] {
-    const char* e = std::getenv("FSMI_BUILD_LDS_KB");
-    return e ? std::atoi(e) : 0;
-  }();
-  const size_t lds_cap = static_cast<size_t>(lds_env > 0 && lds_env <= 160 ? lds_env
-                                              : (B * H * nwt0 * ndc0 > 256 ? 80 : 160)) * 1024;
+  const size_t lds_cap = static_cast<size_t>(B * H * nwt0 * ndc0 > 256 ? 80 : 160) * 1024;
   int GP = kBuildG;
   while (GP > 1 && static_cast<size_t>(build_lds_floats(Cg, Cs, WT, RS, GP)) * sizeof(float) > lds_cap) GP /= 2;
   const size_t lds = static_cast<size_t>(build_lds_floats(Cg, Cs, WT, RS, GP)) * sizeof(float);
@@ -642,8 +624,6 @@ int launch_build_stem(const float* fl, const float* fr, const float* A, const fl
   const int nwt = (W + WT - 1) / WT, ndc = (D + DCH - 1) / DCH;
   const unsigned grid = static_cast<unsigned>(B) * H * nwt * ndc;
   const bool vec = (W % 4) == 0;
-  const char* dbs = std::getenv("FSMI_BUILD_DBG");
-  const int dbg = dbs ? std::atoi(dbs) : 0;
   LaunchTimer t(FSMI_K_COMB, s);
   unsigned long long* clk = clock_slot(FSMI_K_COMB, s, static_cast<long long>(grid) * (nthr / kWave));
 #define FSMI_BUILD_CASE(V, P)                                                                                     \
@@ -654,10 +634,10 @@ int launch_build_stem(const float* fl, const float* fr, const float* A, const fl
       return finish_launch("fsmi_comb_volume_stem: LDS attribute");                                               \
     set_replay(FSMI_K_COMB, s, [=] {                                                                              \
       hipLaunchKernelGGL((build_stem_kernel<V, P>), dim3(grid), dim3(nthr), lds, s, fl, fr, A, Bm, Wg, out, C, Cs,  \
-                         D, H, W, WQ, DQN, nwt, ndc, dbg, nullptr);                                               \
+                         D, H, W, WQ, DQN, nwt, ndc, nullptr);                                                    \
     });                                                                                                           \
     hipLaunchKernelGGL((build_stem_kernel<V, P>), dim3(grid), dim3(nthr), lds, s, fl, fr, A, Bm, Wg, out, C, Cs, D, \
-                       H, W, WQ, DQN, nwt, ndc, dbg, clk);                                                        \
+                       H, W, WQ, DQN, nwt, ndc, clk);                                                             \
   } while (0)
   if (vec) {
     if (GP == 8) FSMI_BUILD_CASE(4, 8);

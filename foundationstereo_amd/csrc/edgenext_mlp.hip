@@ -41,11 +41,10 @@ struct MlpArgs {
   const float2* sb2;               // C pairs (2^-wexp, b2)
   const float* gamma;              // C or nullptr
   int B, HW, tiles;
-  unsigned long long* ts;          // debug (fsmi_debug_conv_timestamps): 8 phase stamps per block
   unsigned long long* clk;         // in-kernel launch clock (nullptr: off)
 };
 
-// gelu_erf_h (conv_halo.h, FSMI_GELU_FAST) on two values at once: the same operations in the same
+// gelu_erf_h (conv_halo.h) on two values at once: the same operations in the same
 // order on <2 x float>, so the fma / mul / add chains issue as packed v_pk_* instructions (two per
 // lane per issue) and every result is bit-identical to the scalar form.  The GELU of the 4C x 64
 // hidden tile is the kernel's largest VALU phase (~30 operations per element, more issue cycles per
@@ -53,7 +52,6 @@ struct MlpArgs {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 gelu_erf_h2(f32x2 x) {
-#if FSMI_GELU_FAST
   const f32x2 z = x * 0.70710678118654752f;
   const f32x2 t = z * z;
   f32x2 p = 7.847259258e-05f;
@@ -82,9 +80,6 @@ __device__ __forceinline__ f32x2 gelu_erf_h2(f32x2 x) {
   const f32x2 big = {copysignf(g.x, z.x), copysignf(g.y, z.y)};
   const f32x2 erf = {fabsf(z.x) < 1.f ? small.x : big.x, fabsf(z.y) < 1.f ? small.y : big.y};
   return 0.5f * x * (1.f + erf);
-#else
-  return f32x2{gelu_erf_h(x.x), gelu_erf_h(x.y)};
-#endif
 }
 
 // max over the block of per-thread values v >= 0 (8 waves); one barrier
@@ -96,15 +91,6 @@ __device__ __forceinline__ float block_max8(float v, float* red, int lane, int w
   const float4 r1 = *reinterpret_cast<const float4*>(red + 4);
   return fmaxf(fmaxf(fmaxf(r0.x, r0.y), fmaxf(r0.z, r0.w)), fmaxf(fmaxf(r1.x, r1.y), fmaxf(r1.z, r1.w)));
 }
-
-// phase stamp k of this block (lane 0 of wave FSMI_MLP_STAMP_WAVE) when the debug buffer is set
-#ifndef FSMI_MLP_STAMP_WAVE
-#define FSMI_MLP_STAMP_WAVE 0
-#endif
-__device__ __forceinline__ void mlp_stamp(const MlpArgs& a, int k) {
-  if (a.ts && threadIdx.x == 64 * FSMI_MLP_STAMP_WAVE) a.ts[static_cast<size_t>(blockIdx.x) * 8 + k] = wall_clock64();
-}
-
 
 template <int C>
 __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
@@ -124,7 +110,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
   const int b = blockIdx.x / a.tiles;
   const int p0 = (blockIdx.x - b * a.tiles) * PX;
   const long long HW = a.HW;
-  mlp_stamp(a, 0);
 
   // W1 fragments of the first two chunks, issued first: their L2 round trip overlaps the x tile's
   const int hrow0 = wave * 32 * TM1;
@@ -167,7 +152,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
     }
   }
   const int sx = __builtin_amdgcn_readfirstlane(chunk_exp(block_max8(mx, red, lane, wave)));
-  mlp_stamp(a, 1);
   const float xs = exp2i(sx == kNoExp ? 0 : sx);
 #pragma unroll
   for (int u = 0; u < XT; ++u) {
@@ -223,7 +207,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
   };
 #pragma unroll
   for (int c = 0; c < kRing; ++c) load_w2(c, c);
-  mlp_stamp(a, 2);
   // bias + GELU in place; row of element r of fragment i: hrow0 + 32 i + (r & 3) + 8 (r >> 2) + 4 hsel
   const float xinv = exp2i(sx == kNoExp ? 0 : -sx);
   float hm = 0.f;
@@ -243,9 +226,7 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
     }
   // the barrier inside block_max8 also retires every wave's reads of the x image, which the
   // hidden image overwrites next
-  mlp_stamp(a, 3);
   const int sh = __builtin_amdgcn_readfirstlane(chunk_exp(block_max8(hm, red, lane, wave)));
-  mlp_stamp(a, 4);
   const float hs = exp2i(sh == kNoExp ? 0 : sh);
   _Float16(*Hh)[HR] = reinterpret_cast<_Float16(*)[HR]>(img);
   _Float16(*Hl)[HR] = reinterpret_cast<_Float16(*)[HR]>(img + PX * HR);
@@ -268,7 +249,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
       }
   __syncthreads();
 
-  mlp_stamp(a, 5);
   // ---- GEMM 2: out rows [32 m2, +32) x px [32 n2, +32), K = E; even / odd k-steps accumulate apart;
   // weights kRing chunks ahead in registers (one chunk's 6 MFMAs are ~200 cycles, an L2 trip ~700)
   f32x16 acc2[2][1][1];
@@ -287,7 +267,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
     }
     if (c + kRing < NKH) load_w2(c % kRing, c + kRing);
   }
-  mlp_stamp(a, 6);
   // epilogue: out = res + gamma * (v * 2^-wexp * 2^-sh + b2)
   const int px = p0 + n2 * 32 + rl;
   if (px < HW) {
@@ -305,7 +284,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
       a.out[base + static_cast<size_t>(co) * HW] = rv[r] + g * v;
     }
   }
-  mlp_stamp(a, 7);
 }
 
 
@@ -313,8 +291,6 @@ __global__ __launch_bounds__(512) void edgenext_mlp_kernel(MlpArgs a) {
 }  // namespace fsmi
 
 using namespace fsmi;
-
-extern unsigned long long* g_conv_ts;   // conv_halo_x3.hip: fsmi_debug_conv_timestamps
 
 extern "C" int fsmi_edgenext_mlp(const float* x, const float* res, float* out, const void* w1hi, const void* w1lo,
                                  const float* sb1, const void* w2hi, const void* w2lo, const float* sb2,
@@ -337,7 +313,6 @@ extern "C" int fsmi_edgenext_mlp(const float* x, const float* res, float* out, c
   a.B = B;
   a.HW = H * W;
   a.tiles = (a.HW + kMlpPX - 1) / kMlpPX;
-  a.ts = g_conv_ts;
   hipStream_t s = as_stream(stream);
   a.clk = clock_slot(FSMI_K_CONV2D, s, 8ll * B * a.tiles, "edgenext_mlp", true);
   LaunchTimer t(FSMI_K_CONV2D, s);

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void volume_pyramid_kernel(const float* __rest
 // L, nchunk/4); one wave = 64 consecutive pixels of one image x 4 geo channels (or the corr
 // channel) of one level.  Coordinates follow bilinear_sampler: x -> 2x/(n-1)-1 -> (x'+1) *
 // ((n-1)/2) (the CPU grid_sampler's align_corners unnormalise), then linear interpolation with
-// zero padding.  (2 or 7 channels per wave, FSMI_LOOKUP_CPC: within 1 % back to back and in the
+// zero padding.  (2 or 7 channels per wave at radius 4: within 1 % of 4 back to back and in the
 // step, round 4.)
 // ---------------------------------------------------------------------------
 struct LookupArgs {
@@ -543,25 +543,16 @@ int fsmi_geo_lookup_coords(const float* const* vol_levels, const float* const* c
                      static_cast<long long>(2 * radius + 1) * HW * 4 < (1ll << 31) &&
                      static_cast<long long>(B) * tiles < (1ll << 31),
                  "fsmi_geo_lookup: a channel plane exceeds 2 GB (D=%d, H*W=%d)", D, HW);
-  // geo channels per wave (FSMI_LOOKUP_CPC: 2 / 4 / 7 at radius 4, an A/B knob)
-  static const int env_cpc = [] { const char* e = getenv("FSMI_LOOKUP_CPC"); const int v = e ? atoi(e) : 4;
-                                  return (v == 2 || v == 7) ? v : 4; }();
-  const int cpc = radius == 4 ? env_cpc : 4;
+  const int cpc = 4;                               // geo channels per wave
   const int nchunk = (Cv + cpc - 1) / cpc + 1;
   dim3 grid(static_cast<unsigned>(B * tiles), num_levels, (nchunk + 3) / 4);
   hipStream_t s = as_stream(stream);
   LaunchTimer t(FSMI_K_LOOKUP, s);
-  auto launch = [grid, radius, s, tiles, cpc](const LookupArgs& la) {
-    if (radius == 4 && cpc == 2) {
-      hipLaunchKernelGGL((geo_lookup_kernel<4, 2>), grid, dim3(256), 0, s, la, tiles);
-    } else if (radius == 4 && cpc == 7) {
-      hipLaunchKernelGGL((geo_lookup_kernel<4, 7>), grid, dim3(256), 0, s, la, tiles);
-    } else {
-      switch (radius) {
-        case 2: hipLaunchKernelGGL((geo_lookup_kernel<2, 4>), grid, dim3(256), 0, s, la, tiles); break;
-        case 3: hipLaunchKernelGGL((geo_lookup_kernel<3, 4>), grid, dim3(256), 0, s, la, tiles); break;
-        default: hipLaunchKernelGGL((geo_lookup_kernel<4, 4>), grid, dim3(256), 0, s, la, tiles); break;
-      }
+  auto launch = [grid, radius, s, tiles](const LookupArgs& la) {
+    switch (radius) {
+      case 2: hipLaunchKernelGGL((geo_lookup_kernel<2, 4>), grid, dim3(256), 0, s, la, tiles); break;
+      case 3: hipLaunchKernelGGL((geo_lookup_kernel<3, 4>), grid, dim3(256), 0, s, la, tiles); break;
+      default: hipLaunchKernelGGL((geo_lookup_kernel<4, 4>), grid, dim3(256), 0, s, la, tiles); break;
     }
   };
   a.clk = nullptr;

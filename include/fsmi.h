@@ -191,11 +191,6 @@ int fsmi_conv3d_direct(const float* x, const float* w, const float* bias, float*
  * or the policy picked for a layer, checked by tests.) */
 int fsmi_conv_launch_counts(long long* counts, int n, int reset);
 
-/* Debug: while buf != NULL, every halo-conv launch stores per-block wall-clock
- * stamps (100 MHz) into buf[block*40 + 0..39]: start, each chunk's staging
- * barrier, before/after the epilogue, (chunks << 32 | block).  NULL disables. */
-int fsmi_debug_conv_timestamps(unsigned long long* buf);
-
 int fsmi_conv2d_halo_x3(const float* const* seg_ptr, const int* seg_ch, const int* seg_ctot, int nseg,
                         const void* whi, const void* wlo, const float* scale_bias, const float* gamma,
                         const float* res, int res_ctot, float* out, int out_ctot, int co0, int B, int Cout,

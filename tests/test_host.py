@@ -50,6 +50,19 @@ def test_library_exports_header_symbols():
     assert lib.fsmi_version() >= 100
 
 
+def test_native_sources_read_one_environment_variable():
+    """The native library takes its policy from its arguments: the only name any source under csrc/
+    passes to getenv is FSMI_BUILD_TILE (the build tile override the ragged-tile parity test uses)."""
+    csrc = os.path.join(REPO, "foundationstereo_amd", "csrc")
+    names, calls = set(), 0
+    for path in (os.path.join(root, f) for root, _, files in os.walk(csrc) for f in files):
+        txt = open(path).read()
+        calls += len(re.findall(r"\bgetenv\b", txt))
+        names |= set(re.findall(r"\bgetenv\s*\(\s*\"([^\"]*)\"", txt))
+    assert names == {"FSMI_BUILD_TILE"}, names
+    assert calls == 1, calls         # and no call whose argument is not a literal
+
+
 def test_fast_library_same_abi(monkeypatch):
     """libfsmi_fast.so (FSMI_PRECISION=fast: one fp16 MFMA product per conv MAC) is a separate build of
     the same C ABI, selected by _lib.library_path(); an unknown precision is refused."""

@@ -24,7 +24,6 @@ CFG = {"cfg1": (256, 320, 64, 128), "cfg2": (480, 640, 192, 128), "cfg2l": (480,
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="cfg2")
 ap.add_argument("--reps", type=int, default=50)
-ap.add_argument("--dbg", type=int, nargs="*", default=[0], help="FSMI_BUILD_DBG values (1 no dots, 2 no stores)")
 ap.add_argument("--tiles", nargs="*", default=["", "16,12", "8,12", "16,6", "8,6", "4,12", "16,16", "8,16"])
 a = ap.parse_args()
 H, W, md, C = CFG[a.config]
@@ -60,13 +59,10 @@ print(f"  two-pass            {us:8.1f} us  {nbytes / us / 1e3:7.0f} GB/s")
 vol = torch.empty_like(ref)
 us = timeit(lambda: vol.fill_(1.0))
 print(f"  torch fill_ (same volume)  {us:8.1f} us  {vol.numel() * 4 / us / 1e3:7.0f} GB/s written")
-for dbg in a.dbg:
-    os.environ["FSMI_BUILD_DBG"] = str(dbg)
-    for tile in a.tiles:
-        os.environ["FSMI_BUILD_TILE"] = tile
-        out = ops.comb_volume_stem(fl, fr, A, Bm, Wg, D4)
-        err = float((out - ref).abs().max())
-        us = timeit(lambda: ops.comb_volume_stem(fl, fr, A, Bm, Wg, D4))
-        print(f"  one-pass dbg{dbg} {tile or 'auto':>8}  {us:8.1f} us  {nbytes / us / 1e3:7.0f} GB/s  max|diff| {err:.1e}")
+for tile in a.tiles:
+    os.environ["FSMI_BUILD_TILE"] = tile
+    out = ops.comb_volume_stem(fl, fr, A, Bm, Wg, D4)
+    err = float((out - ref).abs().max())
+    us = timeit(lambda: ops.comb_volume_stem(fl, fr, A, Bm, Wg, D4))
+    print(f"  one-pass {tile or 'auto':>8}  {us:8.1f} us  {nbytes / us / 1e3:7.0f} GB/s  max|diff| {err:.1e}")
 os.environ.pop("FSMI_BUILD_TILE", None)
-os.environ.pop("FSMI_BUILD_DBG", None)

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """DispHead's EdgeNeXt MLP at cfg2's shape (1, 128, 120, 160): the fused kernel (ops.edgenext_mlp)
 vs the two 1x1 convs it replaces (pwconv1 + GELU, pwconv2 + gamma + residual), each timed as the
-mean over a replayed graph of 20 launches; then one eager fused launch with the debug phase stamps
-(fsmi_debug_conv_timestamps): mean per-block phase durations in us and the launch span.
+mean over a replayed graph of 20 launches.
 GPU box: python tools/mlp_bench.py"""
 import json
 import os
@@ -13,7 +12,7 @@ sys.path.insert(0, REPO)
 
 import torch  # noqa: E402
 
-from foundationstereo_amd import _lib, ops, synth, update  # noqa: E402
+from foundationstereo_amd import ops, synth, update  # noqa: E402
 from foundationstereo_amd.submodule import EdgeNextConvEncoder  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -51,19 +50,7 @@ with torch.no_grad():
         fused = timed(lambda: ops.edgenext_mlp(x, y, pk1, b1, pk2, b2, gamma=enc.gamma, out=out))
         two = timed(lambda: update._conv(enc.pwconv2, [update._conv(enc.pwconv1, [x], "gelu")], gamma=enc.gamma,
                                          res=y))
-        # phase stamps of one eager launch (100 MHz wall clock)
-        nblk = B * ((H * W + 63) // 64)
-        ts = torch.zeros(nblk * 8, dtype=torch.int64, device=dev)
-        _lib.load().fsmi_debug_conv_timestamps(ts.data_ptr())
-        ops.edgenext_mlp(x, y, pk1, b1, pk2, b2, gamma=enc.gamma, out=out)
-        torch.cuda.synchronize()
-        _lib.load().fsmi_debug_conv_timestamps(None)
-        st = ts.view(nblk, 8).double().cpu() / 100.0       # us
-        names = ["x_load+max", "split+gemm1", "gelu", "hmax_bar", "h_split", "gemm2", "epilogue"]
-        ph = {n: round(float((st[:, k + 1] - st[:, k]).mean()), 2) for k, n in enumerate(names)}
-        ph["block"] = round(float((st[:, 7] - st[:, 0]).mean()), 2)
-        ph["span"] = round(float(st[:, 7].max() - st[:, 0].min()), 2)
         flops = 2 * 2 * 128 * 512 * B * H * W
         res[f"B{B}"] = {"fused_us": round(fused, 2), "two_conv_us": round(two, 2),
-                        "fused_TFLOPs": round(flops / fused / 1e6, 1), "phases_us": ph}
+                        "fused_TFLOPs": round(flops / fused / 1e6, 1)}
 print(json.dumps(res), flush=True)
