@@ -76,6 +76,8 @@ SIGNATURES = {
     "fsmi_photo_consistency": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I] + [ctypes.c_longlong] * 8 +
                               [ctypes.POINTER(_F), _I, ctypes.c_double, _I, _P],
     "fsmi_photo_consistency_ws_bytes": [_I, _I, _I, _I],
+    "fsmi_disp_confidence": [_P, _I, _I, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P, _P],
+    "fsmi_risk_coverage": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "fsmi_frames_ingest": [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _I, _I, _I, _I, _I, _I, _I, _P],
     "fsmi_disp_minmax": [_P, _P, _I, _I, _I, _F, _P],
     "fsmi_disp_colorize": [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P],

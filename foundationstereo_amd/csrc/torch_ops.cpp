@@ -425,6 +425,69 @@ std::tuple<Tensor, Tensor, Tensor> disp_metrics(const Tensor& pred_, const Tenso
   return {table, sums, error};
 }
 
+// ops.disp_confidence: (mass, spread, peak, entropy); a map not asked for is empty
+std::tuple<Tensor, Tensor, Tensor, Tensor> disp_confidence(const Tensor& logits_, const c10::optional<Tensor>& disp_,
+                                                           int64_t up, c10::optional<double> disp_scale, double radius,
+                                                           bool want_mass, bool want_spread, bool want_peak,
+                                                           bool want_entropy) {
+  const c10::DeviceGuard guard(logits_.device());
+  check_dev("disp_confidence", logits_);
+  TORCH_CHECK(logits_.dim() == 4, "disp_confidence: logits must be (B,D,h,w)");
+  TORCH_CHECK(up >= 1 && up <= FSMI_CONF_MAX_UP, "disp_confidence: up in 1..", FSMI_CONF_MAX_UP);
+  TORCH_CHECK(want_mass || want_spread || want_peak || want_entropy, "disp_confidence: no output asked for");
+  Tensor logits = logits_.contiguous(), disp;       // any 4-byte aligned base: the entry point picks the access width
+  const int64_t B = logits.size(0), D = logits.size(1), h = logits.size(2), w = logits.size(3);
+  TORCH_CHECK(B >= 1 && h >= 1 && w >= 1 && D >= 1 && D <= FSMI_CONF_MAX_D, "disp_confidence: D in 1..", FSMI_CONF_MAX_D,
+              ", no empty axis");
+  const int64_t H = h * up, W = w * up;
+  TORCH_CHECK(H * W <= INT32_MAX, "disp_confidence: H*W exceeds 2^31 - 1");
+  if (disp_.has_value() && disp_->defined()) {
+    check_dev("disp_confidence", *disp_);
+    TORCH_CHECK(disp_->dim() == 3 && disp_->size(0) == B && disp_->size(1) == H && disp_->size(2) == W &&
+                    disp_->device() == logits.device(),
+                "disp_confidence: disp must be (B,h*up,w*up) on the device of logits");
+    disp = disp_->contiguous();
+  }
+  auto map = [&](bool want) { return want ? at::empty({B, H, W}, logits.options()) : at::empty({0}, logits.options()); };
+  Tensor mass = map(want_mass), spread = map(want_spread), peak = map(want_peak), entropy = map(want_entropy);
+  ok(fsmi_disp_confidence(cp(logits), (int)B, (int)D, (int)h, (int)w, disp.defined() ? cp(disp) : nullptr, (int)up,
+                          disp_scale.has_value() ? (float)*disp_scale : (float)(1.0 / (double)up), (float)radius,
+                          want_mass ? mp(mass) : nullptr, want_spread ? mp(spread) : nullptr,
+                          want_peak ? mp(peak) : nullptr, want_entropy ? mp(entropy) : nullptr, stream_of(logits)),
+     "disp_confidence");
+  return {mass, spread, peak, entropy};
+}
+
+// ops.risk_coverage: (count, err_q20, dropped)
+std::tuple<Tensor, Tensor, Tensor> risk_coverage(const c10::optional<Tensor>& conf_, const Tensor& pred_, const Tensor& gt_,
+                                                 const c10::optional<Tensor>& mask_, int64_t nbins, double err_bin_scale) {
+  const c10::DeviceGuard guard(pred_.device());
+  check_dev("risk_coverage", pred_); check_dev("risk_coverage", gt_);
+  TORCH_CHECK(pred_.dim() == 3 && gt_.sizes() == pred_.sizes() && gt_.device() == pred_.device(),
+              "risk_coverage: pred, gt must be (B,H,W) alike on one device");
+  TORCH_CHECK(nbins >= 2 && nbins <= FSMI_RISK_MAX_BINS, "risk_coverage: nbins in 2..", FSMI_RISK_MAX_BINS);
+  const int64_t B = pred_.size(0), H = pred_.size(1), W = pred_.size(2);
+  TORCH_CHECK(B >= 1 && H >= 1 && W >= 1 && H * W <= INT32_MAX, "risk_coverage: bad shape");
+  Tensor conf;
+  if (conf_.has_value() && conf_->defined()) {
+    check_dev("risk_coverage", *conf_);
+    TORCH_CHECK(conf_->sizes() == pred_.sizes() && conf_->device() == pred_.device(),
+                "risk_coverage: conf must have the shape and device of pred");
+    conf = conf_->contiguous();
+  }
+  Tensor mask = mask_arg("risk_coverage", mask_, B, H, W, pred_, "pred", false);
+  Tensor pred = pred_.contiguous(), gt = gt_.contiguous();
+  const auto i64 = pred.options().dtype(at::kLong);
+  Tensor count = at::empty({B, nbins}, i64), err_q20 = at::empty({B, nbins}, i64), dropped = at::empty({B}, i64);
+  ok(fsmi_risk_coverage(conf.defined() ? cp(conf) : nullptr, cp(pred), cp(gt),
+                        mask.defined() ? mask.data_ptr<uint8_t>() : nullptr, (int)B, (int)H, (int)W, (int)nbins,
+                        (float)err_bin_scale, reinterpret_cast<long long*>(count.data_ptr<int64_t>()),
+                        reinterpret_cast<long long*>(err_q20.data_ptr<int64_t>()),
+                        reinterpret_cast<long long*>(dropped.data_ptr<int64_t>()), stream_of(pred)),
+     "risk_coverage");
+  return {count, err_q20, dropped};
+}
+
 Tensor gt_decode(const Tensor& gt_u8_, double gt_scale) {
   const c10::DeviceGuard guard(gt_u8_.device());
   check_u8("gt_decode", gt_u8_);
@@ -585,6 +648,14 @@ TORCH_LIBRARY(fsmi, m) {
   m.def("disp_metrics(Tensor pred, Tensor gt, Tensor? mask=None, float[] thresholds=[1.0, 3.0, 5.0], "
         "float gt_scale=1000.0, bool want_error=False) -> (Tensor, Tensor, Tensor)");
   m.def("gt_decode(Tensor gt_u8, float gt_scale=1000.0) -> Tensor");
+  // confidence from the classifier's logits (include/fsmi.h): (mass, spread, peak, entropy); disp_scale=None is
+  // 1 / up; a map not asked for is empty
+  m.def("disp_confidence(Tensor logits, Tensor? disp=None, int up=4, float? disp_scale=None, float radius=1.0, "
+        "bool want_mass=True, bool want_spread=True, bool want_peak=True, bool want_entropy=True) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
+  // the sparsification histogram: (count, err_q20, dropped); conf=None bins by the error itself
+  m.def("risk_coverage(Tensor? conf, Tensor pred, Tensor gt, Tensor? mask=None, int nbins=256, "
+        "float err_bin_scale=16.0) -> (Tensor, Tensor, Tensor)");
   // a whole sequence of maps (train/losses.py:379-498): (table, sums, loss); max_disparity=None is +inf, no clamp
   m.def("seq_metrics(Tensor[] preds, Tensor gt, Tensor? mask=None, float[] thresholds=[1.0, 3.0, 5.0], "
         "float? max_disparity=None, float beta=1.0, float[]? weights=None, int[] smooth_rows=[], "
@@ -611,5 +682,7 @@ TORCH_LIBRARY_IMPL(fsmi, CUDA, m) {
   m.impl("vis_disparity", vis_disparity);
   m.impl("disp_metrics", disp_metrics);
   m.impl("gt_decode", gt_decode);
+  m.impl("disp_confidence", disp_confidence);
+  m.impl("risk_coverage", risk_coverage);
   m.impl("seq_metrics", seq_metrics);
 }

@@ -14,8 +14,11 @@ reference; ``visibility``) draw the picture and build the clouds from the VISIBL
 ``photometric``) scores the disparity against the two frames without a ground truth: it writes ``warped.png``
 (the right frame in the left view) and ``photometric.png`` (the residual, 0 .. ``--photo_max`` grey levels) and
 adds ``"photometric"`` and ``"row_offset"``, the rig's vertical misalignment probed over -2 .. 2 rows, to the
-line.  ``--synthetic`` runs without a checkpoint on the
-hash-initialised model the tests use.
+line.  ``--confidence 1`` (not in the reference; ``confidence``) reads the cost volume's own certainty of the
+disparity: it writes ``confidence.png`` (the ``mass`` channel, 0 .. 1 over the turbo table) and adds
+``"confidence": {"mass_mean", "entropy_mean", "spread_mean_px"}`` to the line; ``--min_confidence T`` drops the
+pixels with ``mass < T`` from picture and clouds (ANDed with the visibility mask when a check is on).
+``--synthetic`` runs without a checkpoint on the hash-initialised model the tests use.
 """
 from __future__ import annotations
 
@@ -36,7 +39,8 @@ VISIBILITY_GREY = (255, 0, 64, 128, 192)
 
 def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid_iters=32, camera_type="pinhole",
              z_far=10.0, remove_invisible=1, denoise_cloud=1, denoise_nb_points=30, denoise_radius=0.03,
-             get_pc=1, occlusion_check=0, lr_check=0, occlusion_tol=1.0, lr_thresh=1.0, photo_check=0) -> dict:
+             get_pc=1, occlusion_check=0, lr_check=0, occlusion_tol=1.0, lr_thresh=1.0, photo_check=0,
+             confidence=0, min_confidence=0.0) -> dict:
     """scripts/run_demo.py:131-275 for one pair of uint8 frames (arrays or device tensors).  Returns
     device tensors: ``disp`` (H,W), ``vis`` (H,2W,3) uint8, ``minmax`` (2), ``depth`` (H,W), ``cloud`` and
     ``cloud_denoise`` as (points (M,3), colors (M,3) uint8) -- the last three None without ``get_pc``,
@@ -46,8 +50,13 @@ def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid
     disparity with every other class set to +inf, and only VISIBLE pixels enter the clouds; ``disp``
     stays the forward's.  With ``photo_check``, ``photometric`` is ``photometric.consistency``'s result (with the
     warped frame and the maps, over the VISIBLE pixels when a check is on) and ``row_probe``
-    ``photometric.row_probe``'s over -2 .. 2 rows."""
+    ``photometric.row_probe``'s over -2 .. 2 rows.  With ``confidence`` or ``min_confidence`` > 0 the forward
+    keeps its logits (``model.keep_logits``, restored afterwards; with ``hiera`` those of the full-resolution
+    pass), ``confidence`` is ``confidence.from_model``'s result unpadded to (1,H,W) maps, and with
+    ``min_confidence`` = T > 0 the pixels with ``mass < T`` (NaN included) are drawn black and left out of the
+    clouds, ANDed with the VISIBLE set when a check is on; ``keep`` is then that bool (1,H,W) mask."""
     check = bool(occlusion_check) or bool(lr_check)
+    want_conf = bool(confidence) or min_confidence > 0
     if photo_check and camera_type != "pinhole":
         raise ValueError("run_pair: photo_check warps a rectified pinhole pair (a pixel moves along its row by its "
                          f"disparity); camera_type {camera_type!r} is refused")
@@ -59,11 +68,23 @@ def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid
     fr = frames.ingest(left_u8, right_u8, scale=scale)
     if len(fr.batch) != 1:
         raise ValueError(f"run_pair: one pair at a time, got a batch of {len(fr.batch)}")
-    with torch.no_grad():
-        if not hiera:
-            disp = model.forward(fr.left, fr.right, iters=valid_iters, test_mode=True)
-        else:
-            disp = model.run_hierachical(fr.left, fr.right, iters=valid_iters, test_mode=True, small_ratio=0.5)
+    kept = getattr(model, "keep_logits", False)
+    if want_conf:
+        model.keep_logits = True
+    try:
+        with torch.no_grad():
+            if not hiera:
+                disp = model.forward(fr.left, fr.right, iters=valid_iters, test_mode=True)
+            else:
+                disp = model.run_hierachical(fr.left, fr.right, iters=valid_iters, test_mode=True, small_ratio=0.5)
+    finally:
+        if want_conf:
+            model.keep_logits = kept
+    conf = None
+    if want_conf:
+        from . import confidence as _conf
+        c = _conf.from_model(model, disp.float())                           # on the padded grid, then unpadded like disp
+        conf = _conf.Confidence(*[fr.padder.unpad(getattr(c, n)[:, None])[:, 0] for n in _conf.CHANNELS])
     disp = fr.padder.unpad(disp.float())                                    # run_demo.py:166
     vis_cls, drawn = None, disp
     if check:
@@ -74,22 +95,29 @@ def run_pair(model, left_u8, right_u8, K, baseline, *, scale=1.0, hiera=0, valid
         vis_cls = visibility.classify(disp, right, occlusion=bool(occlusion_check), occlusion_tol=occlusion_tol,
                                       lr_thresh=lr_thresh)
         drawn = visibility.invalidate(disp, vis_cls.classes)
+    keep = vis_cls.visible if check else None
+    if min_confidence > 0:
+        sure = conf.mass >= min_confidence                                  # NaN compares false
+        keep = sure if keep is None else keep & sure
+        drawn = drawn.masked_fill(~sure[:, None], float("inf"))
     other = {}
     vis = frames.vis_disparity(drawn[:, 0], image=fr.image_u8, other_output=other)
     out = {"disp": disp[0, 0], "vis": vis[0], "minmax": other["minmax"][0], "frames": fr,
            "depth": None, "cloud": None, "cloud_denoise": None}
     if check:
         out["visibility"] = vis_cls
+    if want_conf:
+        out["confidence"], out["keep"] = conf, keep
     if photo_check:
         from . import photometric
-        lv, rv, keep = fr.padder.unpad(fr.left), fr.padder.unpad(fr.right), vis_cls.visible if check else None
-        out["photometric"] = photometric.consistency(disp, lv, rv, keep, want_warped=True)
-        out["row_probe"] = photometric.row_probe(disp, lv, rv, keep, max_offset=2.0, step=1.0)
+        lv, rv, seen = fr.padder.unpad(fr.left), fr.padder.unpad(fr.right), vis_cls.visible if check else None
+        out["photometric"] = photometric.consistency(disp, lv, rv, seen, want_warped=True)
+        out["row_probe"] = photometric.row_probe(disp, lv, rv, seen, max_offset=2.0, step=1.0)
     if get_pc:
         c = cloud.disparity_to_cloud(disp, K, baseline, image=fr.image_u8, denoise=bool(denoise_cloud),
                                      nb_points=denoise_nb_points, radius=denoise_radius, scale=scale,
                                      camera_type=camera_type, remove_invisible=bool(remove_invisible), z_far=z_far,
-                                     keep=vis_cls.visible if check else None)[0]
+                                     keep=keep)[0]
         out["depth"] = c.depth
         out["cloud"] = (c.xyz_map[c.valid], fr.image_u8[0][c.valid])
         if denoise_cloud:
@@ -130,6 +158,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--photo_check", type=int, default=0,
                    help="Score the disparity against the two frames: warped.png, photometric.png, residual and row offset in the JSON line")
     p.add_argument("--photo_max", type=float, default=32.0, help="Residual in grey levels at the top of photometric.png's colour range")
+    p.add_argument("--confidence", type=int, default=0, nargs="?", const=1,
+                   help="Read the cost volume's own certainty of the disparity: confidence.png and its means in the JSON line")
+    p.add_argument("--min_confidence", type=float, default=0.0,
+                   help="Drop pixels whose confidence (mass) is below this from picture and clouds (0 = off)")
     p.add_argument("--synthetic", action="store_true",
                    help="No checkpoint: the hash-initialised model of the tests (synth.make_args + synth.init_module_)")
     p.add_argument("--max_disp", type=int, default=192, help="With --synthetic: the model's max_disp")
@@ -163,10 +195,20 @@ def photo_summary(ph, b: int = 0) -> dict:
             "photometric": row[pm.PHOTOMETRIC], "n_scored": int(row[pm.N_SCORED]), "n_ssim": int(row[pm.N_SSIM])}
 
 
+def confidence_summary(conf, b: int = 0) -> dict:
+    """The JSON object of pair ``b`` of a ``confidence`` result (one read-back): the means over the finite
+    pixels; ``spread`` in full-resolution pixels (4 per bin)."""
+    row = torch.stack([torch.nanmean(conf.mass[b].double()), torch.nanmean(conf.entropy[b].double()),
+                       4.0 * torch.nanmean(conf.spread[b].double())]).cpu().tolist()
+    return {"mass_mean": row[0], "entropy_mean": row[1], "spread_mean_px": row[2]}
+
+
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     if not 0 < a.scale <= 1:
         raise SystemExit("scale must be in (0, 1]")                           # run_demo.py:149
+    if not 0 <= a.min_confidence <= 1:
+        raise SystemExit("demo: --min_confidence is a probability: 0 (off) .. 1")
     check = bool(a.occlusion_check) or bool(a.lr_check)
     if check and a.camera_type != "pinhole":
         raise SystemExit("demo: --occlusion_check / --lr_check model a rectified pinhole pair; "
@@ -189,7 +231,7 @@ def main(argv=None) -> dict:
                    denoise_cloud=a.denoise_cloud, denoise_nb_points=a.denoise_nb_points,
                    denoise_radius=a.denoise_radius, get_pc=a.get_pc, occlusion_check=a.occlusion_check,
                    lr_check=a.lr_check, occlusion_tol=a.occlusion_tol, lr_thresh=a.lr_thresh,
-                   photo_check=a.photo_check)
+                   photo_check=a.photo_check, confidence=a.confidence, min_confidence=a.min_confidence)
     fr = out["frames"]
     res = {"out_dir": a.out_dir, "image_size": list(out["disp"].shape), "padded_size": list(fr.batch.shape[-2:]),
            "min_disp": float(out["minmax"][0]), "max_disp": float(out["minmax"][1])}
@@ -212,6 +254,10 @@ def main(argv=None) -> dict:
         res["photometric"] = photo_summary(ph)
         off = float(probe.offset[0])
         res["row_offset"] = off if off == off else None                         # NaN: the minimum is not bracketed
+    if a.confidence:
+        frames.write_png(path("confidence.png"), frames.vis_disparity(out["confidence"].mass, min_val=0.0, max_val=1.0)[0])
+        res["confidence_png"] = path("confidence.png")
+        res["confidence"] = confidence_summary(out["confidence"])
     if a.get_pc:
         cloud.write_ply(path("cloud.ply"), *out["cloud"])                     # run_demo.py:255
         res["cloud"], res["cloud_points"] = path("cloud.ply"), int(out["cloud"][0].shape[0])

@@ -26,7 +26,11 @@ disparity against the two frames instead (``photometric``: the right frame warpe
 residual, and the residual with the right frame N rows up and down): they add ``"photometric"`` and
 ``"row_probe"`` objects to the line, need ``--left_file`` and ``--right_file`` and no ground truth (``--gt_file`` may be
 left out with either; the line then has no ground-truth fields).  With ``--noc`` their mask is the visible
-set.  Prints one JSON line.
+set.  ``--confidence`` (the demo's flag; needs the model run, so not with ``--pred_file``) adds a ``"confidence"``
+object: the means of the cost volume's own confidence maps (``confidence``) and, with a ground truth, how well
+each ranks the pixels by their error: ``ause_mass``, ``ause_entropy``, ``ause_peak`` (area under the sparsification
+error, ``metrics.sparsification``; 0 is the oracle ranking) and ``oracle_area``, over the mask of the flags.
+Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -102,12 +106,31 @@ def score_mask(a, gt: torch.Tensor, device):
     return None
 
 
-def predict(a, device) -> torch.Tensor:
-    """The model's unpadded disparity (H,W) of the pair: demo.run_pair's own ingest, forward and unpad,
-    without the cloud (it reads no intrinsics then; its picture, two launches, is not used)."""
+def predict(a, device):
+    """(the model's unpadded disparity (H,W) of the pair, its confidence maps or None): demo.run_pair's own
+    ingest, forward and unpad, without the cloud (it reads no intrinsics then; its picture, two launches, is
+    not used)."""
     model = demo.load_model(a, device)
     left, right = frames.read_image(a.left_file), frames.read_image(a.right_file)
-    return demo.run_pair(model, left, right, None, None, hiera=a.hiera, valid_iters=a.valid_iters, get_pc=0)["disp"]
+    out = demo.run_pair(model, left, right, None, None, hiera=a.hiera, valid_iters=a.valid_iters, get_pc=0,
+                        confidence=a.confidence)
+    return out["disp"], out.get("confidence")
+
+
+def confidence_fields(conf, pred: torch.Tensor, gt, mask, gt_scale: float) -> dict:
+    """--confidence: the object it adds to the line.  ``conf`` (1,H,W) maps, ``pred`` (H,W); ``gt`` None, fp32
+    (H,W) or the uint8 encoding; ``mask`` (1,H,W) or None.  One read-back."""
+    res = demo.confidence_summary(conf)
+    if gt is None:
+        return {"confidence": res}
+    g = metrics.decode_gt(gt, gt_scale) if gt.dtype == torch.uint8 else gt
+    oracle = metrics.sparsification(None, pred, g, mask)
+    names = ("mass", "entropy", "peak")
+    ranked = [metrics.sparsification(getattr(conf, n), pred, g, mask) for n in names]
+    flat = torch.stack([s.ause(oracle) for s in ranked] + [oracle.area(), ranked[0].dropped[0].double()]).cpu().tolist()
+    res.update({f"ause_{n}": v for n, v in zip(names, flat)})
+    res["oracle_area"], res["n_dropped"] = flat[3], int(flat[4])
+    return {"confidence": res}
 
 
 def predict_sequence(a, device):
@@ -214,8 +237,9 @@ def photo_fields(a, pred: torch.Tensor, mask, device) -> dict:
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     photo = a.photometric or a.row_probe != 0
-    if a.gt_file is None and not photo:
-        raise SystemExit("evaluate: the following arguments are required: --gt_file (optional only with --photometric / --row_probe)")
+    if a.gt_file is None and not (photo or a.confidence):
+        raise SystemExit("evaluate: the following arguments are required: --gt_file (optional only with --photometric / "
+                         "--row_probe / --confidence)")
     if not 0 <= a.row_probe <= 3:
         raise SystemExit("evaluate: --row_probe N probes the offsets -N..N, at most 8 of them: N in 0..3")
     if photo and a.pred_file is not None and not (_given(argv, "--left_file") and _given(argv, "--right_file")):
@@ -223,6 +247,11 @@ def main(argv=None) -> dict:
                          "residual is between the two frames")
     if photo and a.per_iter:
         raise SystemExit("evaluate: --photometric / --row_probe score one disparity: not with --per_iter")
+    if a.confidence and (a.pred_file is not None or a.per_iter):
+        raise SystemExit("evaluate: --confidence reads the cost volume of the model run: not with --pred_file or --per_iter")
+    if a.min_confidence != 0:
+        raise SystemExit("evaluate: --min_confidence drops pixels from the demo's picture and clouds; a score over the "
+                         "confident pixels only is the sparsification curve --confidence reports")
     if a.scale != 1:
         raise SystemExit("evaluate: --scale must be 1: resizing a ground truth is not defined here")
     if a.noc and a.all_pixels:
@@ -239,8 +268,9 @@ def main(argv=None) -> dict:
         if pred.ndim != 2:
             raise SystemExit(f"evaluate: {a.pred_file}: expected a disparity map (H,W), got {pred.shape}")
         pred = torch.from_numpy(np.ascontiguousarray(pred, dtype=np.float32)).to(device)
+        conf = None
     else:
-        pred = predict(a, device)
+        pred, conf = predict(a, device)
     if a.gt_file is None:
         # no ground truth: --noc takes the visible set of the disparity itself
         if a.all_pixels or a.error_png is not None:
@@ -250,7 +280,10 @@ def main(argv=None) -> dict:
             from . import visibility
             mask = visibility.classify(pred, occlusion_tol=a.occlusion_tol).visible
         res = {"mode": "pred_file" if a.pred_file is not None else "model", "image_size": list(pred.shape)}
-        res.update(photo_fields(a, pred, mask, device))
+        if photo:
+            res.update(photo_fields(a, pred, mask, device))
+        if conf is not None:
+            res.update(confidence_fields(conf, pred, None, mask, a.gt_scale))
         if a.noc:
             res["mask"] = "noc"
         print(json.dumps(res))
@@ -275,6 +308,8 @@ def main(argv=None) -> dict:
         res["mask"] = "noc"
     if photo:
         res.update(photo_fields(a, pred, mask, device))
+    if conf is not None:
+        res.update(confidence_fields(conf, pred, gt, mask, a.gt_scale))
     print(json.dumps(res))
     return res
 

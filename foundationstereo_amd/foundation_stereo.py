@@ -246,6 +246,10 @@ class FoundationStereo(nn.Module):
         r = self.args.corr_radius
         self.dx = torch.linspace(-r, r, 2 * r + 1, requires_grad=False).reshape(1, 1, 2 * r + 1, 1)
         self.fused_volume = True
+        # plain attributes (no buffers: state_dict is the reference's).  keep_logits: the forward leaves the
+        # classifier's fp32 logits (B, max_disp / 4, H / 4, W / 4) in last_logits for ``confidence``
+        self.keep_logits = False
+        self.last_logits = None
 
     # ------------------------------------------------------------ volume build
     def _stem_weights(self):
@@ -313,7 +317,13 @@ class FoundationStereo(nn.Module):
         ``foundation_stereo.RANGE_GUARD = False`` to skip it.  A captured forward ends with a
         device-side check instead: every returned disparity tensor (test mode's one, or
         ``init_disp`` and each of ``disp_preds``) is NaN-filled when the flag is set
-        (ops.range_poison_)."""
+        (ops.range_poison_).
+
+        With ``self.keep_logits`` set, the classifier's fp32 logits of this forward stay in
+        ``self.last_logits`` (``confidence.from_model``); the classifier then also runs when ``init_disp``
+        is given, which stays the disparity the refinement starts from.  Under capture the tensor is
+        graph-static memory, valid until the next replay, and is range-poisoned along with the outputs.
+        With the flag off (the default) nothing is kept and nothing extra runs."""
         def run():
             return self._forward(image1, image2, iters, flow_init, test_mode, low_memory, init_disp)
         if not (image1.is_cuda and RANGE_GUARD):
@@ -322,11 +332,16 @@ class FoundationStereo(nn.Module):
             # a captured forward cannot synchronise: its last node NaN-fills the disparity when the
             # flag is set, so a replay that overflowed never returns a finite result (ShardedStereo
             # reads the flag after a replay and recovers)
-            return _poison_outputs(run())
+            out = _poison_outputs(run())
+            if self.keep_logits and self.last_logits is not None:
+                self.last_logits = _poison_outputs(self.last_logits)
+            return out
         return ops.guarded(run)
 
     def _forward(self, image1, image2, iters=12, flow_init=None, test_mode=False, low_memory=False, init_disp=None):
         B = len(image1)
+        if not self.keep_logits:
+            self.last_logits = None        # nothing is kept with the flag off, an earlier forward's logits included
         image1 = normalize_image(image1)
         image2 = normalize_image(image2)
         mp = self.args.mixed_precision
@@ -388,12 +403,15 @@ class FoundationStereo(nn.Module):
                 geo_fn = Combined_Geo_Encoding_Volume(features_left[0].float(), features_right[0].float(),
                                                       vol.float(), num_levels=self.args.corr_levels, dx=self.dx,
                                                       init_corr_pyramid=corr_pyr)
-            if init_disp is None:
+            if init_disp is None or self.keep_logits:
                 cl = self.classifier
                 head = cl[2]   # Conv3d(14, 1, 7, padding=3): direct gfx950 kernel (MIOpen: ~1 TFLOP/s here)
                 logits = ops.conv3d_direct(cl[1](cl[0](vol)).float(), head.weight.float(),
                                            head.bias.float()).squeeze(1)
-                init_disp = ops.softmax_regression(logits)
+                if self.keep_logits:
+                    self.last_logits = logits
+                if init_disp is None:      # a given one stays (run_hierachical's second pass)
+                    init_disp = ops.softmax_regression(logits)
             if ctx_s is not None:
                 streams.join(main, ctx_s, stem_2x, *net_list, *inp_list, *att, *(ctx_pre or ()))
 

@@ -208,3 +208,59 @@ class MetricsAccumulator:
                 "thresholds": list(self.thresholds),
                 "per_pair": {k: float(v) for k, v in per_pair.items()},
                 "pooled": {k: float(v) for k, v in pooled.items()}}
+
+
+# ---------------------------------------------------------------- sparsification (risk-coverage)
+
+ERR_Q20 = float(2 ** 20)            # err_q20 counts |pred - gt| in units of 2^-20 px (include/fsmi.h)
+
+
+@dataclass
+class Sparsification:
+    """``sparsification``'s result: exact integers on the device, one row per pair.  Bin 0 holds the
+    least confident pixels, the first to be removed."""
+    count: Tensor                   # (B,nbins) int64: pixels per confidence bin
+    err_q20: Tensor                 # (B,nbins) int64: their summed |pred - gt|, each capped at 4096 px, x 2^20
+    dropped: Tensor                 # (B) int64: valid pixels left out (pred not finite, confidence outside [0, 1])
+
+    def curve(self, b: int = 0):
+        """(f, m) of pair ``b``, fp64 on the device: after the ``j`` lowest bins are removed, R_j pixels
+        remain with mean error m_j = E_j / 2^20 / R_j at removed fraction f_j = 1 - R_j / R_0; j = 0 ..
+        nbins - 1, points with R_j = 0 dropped (the boolean index synchronises)."""
+        R = self.count[b].flip(0).cumsum(0).flip(0)     # R_j = sum_{k >= j} n_k, still int64
+        E = self.err_q20[b].flip(0).cumsum(0).flip(0)
+        keep = R > 0
+        R, E = R.double(), E.double()
+        R, E = R[keep], E[keep]
+        return 1.0 - R / R[0] if len(R) else R, E / ERR_Q20 / R
+
+    def area(self, b: int = 0) -> Tensor:
+        """The area under ``curve(b)``, trapezoids over f: a 0-d fp64 device tensor (0 for an empty or
+        one-point curve)."""
+        f, m = self.curve(b)
+        if len(f) < 2:
+            return torch.zeros((), dtype=torch.float64, device=self.count.device)
+        return ((f[1:] - f[:-1]) * (m[1:] + m[:-1]) * 0.5).sum()
+
+    def ause(self, oracle: "Sparsification", b: int = 0) -> Tensor:
+        """Area under the sparsification error: ``area - oracle.area``, the oracle being the same call
+        with ``conf=None``; 0 for a confidence that ranks the pixels as their error does."""
+        return self.area(b) - oracle.area(b)
+
+
+def sparsification(conf: Optional[Tensor], pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, nbins: int = 256,
+                   err_cap: float = 16.0) -> Sparsification:
+    """Grade a confidence map in [0, 1] (1 = sure) by the error of the pixels it would remove first:
+    the risk-coverage histogram of ``ops.risk_coverage`` over ``nbins`` equal confidence bins.
+    ``conf=None`` is the oracle ranking, the pixels binned by their own error over [0, ``err_cap``] px
+    (``nbins / err_cap`` bins per px; larger errors share the worst bin).  conf, pred, gt fp32 (H,W),
+    (B,H,W) or (B,1,H,W); validity as ``stereo_metrics``.  A map that is not a probability (``spread``,
+    a photometric residual) goes in as a decreasing function of it, e.g. ``1 / (1 + x)``.  Does not
+    synchronise."""
+    if not float(err_cap) > 0.0:
+        raise ValueError(f"sparsification: err_cap = {err_cap} must be positive")
+    p, g = ops._as_bhw(pred, "sparsification", "pred"), ops._as_bhw(gt, "sparsification", "gt")
+    c = None if conf is None else ops._as_bhw(conf, "sparsification", "conf")
+    m = None if mask is None else ops._as_bhw(mask, "sparsification", "mask")
+    count, err_q20, dropped = ops.risk_coverage(c, p, g, m, nbins, float(nbins) / float(err_cap))
+    return Sparsification(count=count, err_q20=err_q20, dropped=dropped)

@@ -1628,3 +1628,84 @@ def seq_metrics(preds, gt: Tensor, mask: Tensor = None, thresholds=(1.0, 3.0, 5.
                                     _p(mask) if mask is not None else None, cthr, len(thr), float(gt_scale), float(beta),
                                     _p(partials), _p(sums), _p(table), _p(loss), B, H, W, _stream(gt)), "seq_metrics")
     return table, sums, loss
+
+
+# ---------------------------------------------------------------- confidence from the cost volume
+
+CONF_MAX_D = 1024           # FSMI_CONF_MAX_D
+CONF_MAX_UP = 8             # FSMI_CONF_MAX_UP
+CONF_CHANNELS = ("mass", "spread", "peak", "entropy")
+RISK_MAX_BINS = 1024        # FSMI_RISK_MAX_BINS
+
+
+def disp_confidence(logits: Tensor, disp: Tensor = None, up: int = 4, disp_scale: float = None, radius: float = 1.0,
+                    want=CONF_CHANNELS):
+    """Per-pixel confidence from the classifier's logits (include/fsmi.h for the four definitions), one
+    launch.  logits (B,D,h,w) before the softmax; disp None (each column judged at its own expectation)
+    or (B,h*up,w*up), multiplied by ``disp_scale`` (default 1 / up) to give the query in bins ->
+    (mass, spread, peak, entropy), each (B,h*up,w*up) fp32 or None where ``want`` leaves it out.  No host
+    synchronisation."""
+    want = tuple(want)
+    if not want or any(c not in CONF_CHANNELS for c in want):
+        raise RuntimeError(f"disp_confidence: want must name at least one of {CONF_CHANNELS}, got {want}")
+    if not (isinstance(up, int) and 1 <= up <= CONF_MAX_UP):
+        raise RuntimeError(f"disp_confidence: up = {up!r}: an int in 1..{CONF_MAX_UP}")
+    radius = float(radius)
+    if not 0.0 <= radius < float("inf"):
+        raise RuntimeError(f"disp_confidence: radius = {radius} must be finite and >= 0")
+    _check("disp_confidence", logits, *([] if disp is None else [disp]))
+    if logits.dim() != 4:
+        raise RuntimeError(f"disp_confidence: logits must be (B,D,h,w), got {tuple(logits.shape)}")
+    B, D, h, w = logits.shape
+    if not (1 <= D <= CONF_MAX_D and B >= 1 and h >= 1 and w >= 1):
+        raise RuntimeError(f"disp_confidence: logits {tuple(logits.shape)}: D in 1..{CONF_MAX_D}, no empty axis")
+    H, W = h * up, w * up
+    if H * W > 2 ** 31 - 1:
+        raise RuntimeError(f"disp_confidence: H*W = {H * W} exceeds 2^31 - 1")
+    if disp is not None and (tuple(disp.shape) != (B, H, W) or disp.device != logits.device):
+        raise RuntimeError(f"disp_confidence: disp must be ({B},{H},{W}) on the device of logits, got "
+                           f"{tuple(disp.shape)} on {disp.device}")
+    logits = logits.contiguous()           # any 4-byte aligned base goes in: 16-byte accesses only where all are aligned
+    disp = disp.contiguous() if disp is not None else None
+    outs = [torch.empty((B, H, W), device=logits.device, dtype=torch.float32) if c in want else None
+            for c in CONF_CHANNELS]
+    _lib.check(_lib.load().fsmi_disp_confidence(_p(logits), B, D, h, w, _p(disp) if disp is not None else None, up,
+                                                1.0 / up if disp_scale is None else float(disp_scale), radius,
+                                                *[_p(o) if o is not None else None for o in outs], _stream(logits)),
+               "disp_confidence")
+    return tuple(outs)
+
+
+def risk_coverage(conf: Tensor, pred: Tensor, gt: Tensor, mask: Tensor = None, nbins: int = 256,
+                  err_bin_scale: float = 16.0):
+    """The histogram behind the sparsification curve (include/fsmi.h), one launch: pixels binned by
+    ``conf`` in [0, 1] (None: by the error itself, ``nbins - 1 - int(e * err_bin_scale)``, the oracle
+    ranking), per bin the count and the sum of |pred - gt| in units of 2^-20 px.  conf, pred, gt fp32
+    (B,H,W); mask None (valid where gt > 0 and finite) or bool / uint8 (B,H,W) -> (count (B,nbins) int64,
+    err_q20 (B,nbins) int64, dropped (B) int64).  Exact integers; no host synchronisation."""
+    if not (isinstance(nbins, int) and 2 <= nbins <= RISK_MAX_BINS):
+        raise RuntimeError(f"risk_coverage: nbins = {nbins!r}: an int in 2..{RISK_MAX_BINS}")
+    err_bin_scale = float(err_bin_scale)
+    if not 0.0 < err_bin_scale < float("inf"):
+        raise RuntimeError(f"risk_coverage: err_bin_scale = {err_bin_scale} must be finite and positive")
+    _check("risk_coverage", pred, gt, *([] if conf is None else [conf]))
+    if pred.dim() != 3:
+        raise RuntimeError(f"risk_coverage: pred must be (B,H,W), got {tuple(pred.shape)}")
+    B, H, W = pred.shape
+    for name, t in (("gt", gt), ("conf", conf)):
+        if t is not None and (t.shape != pred.shape or t.device != pred.device):
+            raise RuntimeError(f"risk_coverage: {name} must be ({B},{H},{W}) on the device of pred, got "
+                               f"{tuple(t.shape)} on {t.device}")
+    if B < 1 or H < 1 or W < 1 or H * W > 2 ** 31 - 1:
+        raise RuntimeError(f"risk_coverage: bad shape {tuple(pred.shape)}")
+    mask = _mask_arg("risk_coverage", mask, B, H, W, pred.device, "pred")
+    pred, gt = pred.contiguous(), gt.contiguous()
+    conf = conf.contiguous() if conf is not None else None
+    dev = pred.device
+    count = torch.empty((B, nbins), device=dev, dtype=torch.int64)
+    err_q20 = torch.empty((B, nbins), device=dev, dtype=torch.int64)
+    dropped = torch.empty((B,), device=dev, dtype=torch.int64)
+    _lib.check(_lib.load().fsmi_risk_coverage(_p(conf) if conf is not None else None, _p(pred), _p(gt),
+                                              _p(mask) if mask is not None else None, B, H, W, nbins, err_bin_scale,
+                                              _p(count), _p(err_q20), _p(dropped), _stream(pred)), "risk_coverage")
+    return count, err_q20, dropped

@@ -26,7 +26,7 @@ OPS = ("gwc_volume", "concat_volume", "allpairs_corr", "volume_pyramid", "geo_lo
        "disparity_regression", "softmax_regression", "context_upsample", "softmax_context_upsample",
        "disp_to_xyz", "radius_outlier_mask", "disp_visibility", "photo_consistency",
        "frames_ingest", "vis_disparity", "disp_metrics",
-       "gt_decode", "seq_metrics")
+       "gt_decode", "seq_metrics", "disp_confidence", "risk_coverage")
 
 
 def build_extension(force: bool = False, verbose: bool = False) -> str:

@@ -536,6 +536,86 @@ int fsmi_photo_consistency(const float* disp, const void* left, const void* righ
                            void* stream);
 size_t fsmi_photo_consistency_ws_bytes(int B, int H, int W, int n_offsets);
 
+/* ---- confidence: how sure the cost volume was of a disparity -------------
+ * The classifier's logits are a distribution over the D = max_disp / 4 bins of every quarter-resolution
+ * pixel; soft-argmin keeps its mean.  This reads the rest: four per-pixel confidence channels on the
+ * full-resolution grid of the disparity they judge.  Nothing in the reference pins these definitions;
+ * they are stated here and restated in numpy by tests/confidence_oracle.py.  One launch; no host
+ * synchronisation, no allocation, no atomics; capturable in a hipGraph.
+ *
+ * logits: fp32 (B,D,h,w), contiguous, the classifier output before the softmax.  up in 1..8; the maps
+ * are (B,H,W) with H = h * up, W = w * up.  disp: NULL ("self" mode), or fp32 (B,H,W).  mass, spread, peak,
+ * entropy: NULL, or fp32 (B,H,W); at least one is not NULL, a NULL map costs no store.  Every pointer is
+ * 4-byte aligned; disp and the maps are accessed 16 B at a time where up == 4 and all of them are
+ * 16-byte aligned, one float at a time otherwise.  1 <= D <= FSMI_CONF_MAX_D; radius is finite and >= 0; H * W <= 2^31 - 1
+ * (FSMI_ERR_ARG otherwise).
+ *
+ * Output pixel (y, x) of pair b reads the column x_0 .. x_{D-1} = logits[b][.][y / up][x / up] (integer
+ * division: the nearest column, the centre tap of the convex upsampling).  Every operation is
+ * un-contracted fp32 in the order written, every sum starts at 0 and adds d = 0, 1, .. D-1 in order,
+ * divisions and square roots IEEE, expf / logf the device library's:
+ *   m   = max_d x_d                                  t_d = x_d - m          e_d = expf(t_d)
+ *   s   = sum e_d                                    (p_d = e_d / s is the distribution)
+ *   mu  = (sum e_d * (float)d) / s                   the column's expectation, in bins
+ *   var = (sum e_d * (((float)d - mu) * ((float)d - mu))) / s
+ *   set = sum (e_d != 0 ? e_d * t_d : 0)             Hn = logf(s) - set / s        (the entropy, nats)
+ *   q   = disp[b][y][x] * disp_scale                 one multiply: the query, in bins (self mode: q = mu)
+ *   peak    = 1.0f / s                               the largest probability
+ *   entropy = D == 1 ? 1 : min(max(1.0f - Hn / logf((float)D), 0), 1)     (logf((float)D) on the host)
+ *   mass    = min((sum e_d * w_d) / s, 1),  w_d = min(max((radius + 1.0f) - fabsf((float)d - q), 0), 1)
+ *             a trapezoid: full weight within radius bins of q, falling linearly to 0 one bin further,
+ *             so it is continuous in q; for integer q and radius it is the probability within +-radius
+ *             bins.  radius + 1.0f is formed once, on the host.
+ *   spread  = sqrtf(var + (mu - q) * (mu - q))       sqrt(sum p_d (d - q)^2): RMS distance from q, bins
+ * peak, entropy and mass are in [0, 1] (the two clamps only take back a last-bit excess).
+ * A column that holds a NaN or a +inf logit, or only -inf logits, gives NaN in all four maps at its
+ * up x up pixels; -inf logits otherwise count as probability 0.  A non-finite q gives NaN in mass and
+ * spread only.
+ * As built: one lane per column, lanes over w (every plane load coalesced), 64-thread workgroups (at
+ * 640x480, B = 1 there are 19 200 columns for 256 CUs).  The column statistics are computed once per
+ * column.  D <= 128: the column is loaded from HBM once into registers (tiers of 16 / 64 / 128), e_d
+ * replaces x_d there, one expf per element.  Above: three streaming passes, the second and third from
+ * L1 / L2, two expf per element.  Per output pixel only mass needs the column again: the
+ * min(ceil(2 (radius + 1)) + 3, D) bins from floorf(q - (radius + 1)) on that exist are re-read, four bins of each pixel of an output row at a time so
+ * that the loads, L1 / L2 hits, are independent.  (The fp32 difference under the floorf errs by far less
+ * than a bin and the window carries a spare bin at either end, so the bins left out are ones whose fp32
+ * weight is 0; tests/confidence_oracle.py sums all D bins and the device is held to the tolerances there,
+ * not to its bits.)  A lane stores up consecutive floats per output row,
+ * 16 B at a time (and loads disp so) where up == 4 and the bases are 16-byte aligned. */
+#define FSMI_CONF_MAX_D 1024
+#define FSMI_CONF_MAX_UP 8
+int fsmi_disp_confidence(const float* logits, int B, int D, int h, int w, const float* disp_or_null, int up,
+                         float disp_scale, float radius, float* mass, float* spread, float* peak, float* entropy,
+                         void* stream);
+
+/* ---- risk-coverage: grade a confidence by the error of the pixels it would drop first ----
+ * The histogram behind the sparsification curve: pixels binned by confidence, per bin the pixel count
+ * and the sum of |pred - gt|.  Integers throughout, so the result does not depend on the order of the
+ * additions (integer atomics in LDS and global memory) and tests/confidence_oracle.py reproduces it bit
+ * for bit.  One launch after a memset of the three outputs on the same stream; no host synchronisation.
+ *
+ * conf: NULL (the oracle ranking: bin by the error itself), or fp32 (B,H,W).  pred, gt: fp32 (B,H,W).
+ * mask: NULL, or uint8 (B,H,W).  All contiguous; fp32 maps 4-byte aligned.  count, err_q20: int64
+ * (B,nbins); dropped: int64 (B); 8-byte aligned, zeroed by the call itself.  2 <= nbins <=
+ * FSMI_RISK_MAX_BINS, err_bin_scale finite and > 0, H * W <= 2^31 - 1 (FSMI_ERR_ARG otherwise).
+ * Per pixel, un-contracted fp32:
+ *   valid   mask != NULL ? mask != 0 : (gt > 0 and gt finite)         (as fsmi_disp_metrics)
+ *   e     = fabsf(pred - gt)
+ *   a valid pixel whose pred is not finite, or whose c = conf fails 0 <= c <= 1 (NaN fails, -0.0
+ *   passes), adds 1 to dropped[b] and nothing else
+ *   bin   = min(nbins - 1, (int)(c * (float)nbins))                                    conf != NULL
+ *         = nbins - 1 - k,  v = e * err_bin_scale,  k = v < (float)(nbins - 1) ? (int)v : nbins - 1
+ *           (NaN compares false: the worst bin)                                        conf == NULL
+ *   count[b][bin] += 1;   err_q20[b][bin] += (long long)(fminf(e, 4096.0f) * 1048576.0f)
+ * The product by 2^20 is exact and the truncation a function of the value alone; fminf returns 4096
+ * for a NaN e (a non-finite gt under a mask).
+ * As built: 256-thread workgroups, each striding over the pixels of one pair with a (count u32, sum
+ * u64) histogram in LDS, flushed once with one 64-bit global atomic per non-empty bin. */
+#define FSMI_RISK_MAX_BINS 1024
+int fsmi_risk_coverage(const float* conf_or_null, const float* pred, const float* gt,
+                       const unsigned char* mask_or_null, int B, int H, int W, int nbins, float err_bin_scale,
+                       long long* count, long long* err_q20, long long* dropped, void* stream);
+
 /* ---- around the forward: frame ingest and the disparity picture -----------
  * uint8 frames in, uint8 pictures out (with the cloud section, the exceptions to the all-fp32
  * convention).  Nothing below synchronises the host; all of it can be captured in a hipGraph.
