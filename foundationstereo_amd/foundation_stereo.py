@@ -128,12 +128,16 @@ class hourglass(nn.Module):
 
     def forward(self, x, features, gates=None):
         """``gates``: precomputed ``gate_logits(features)`` (ready on the current stream)."""
-        dt_s = None
-        if _update.OVERLAP and self._dt_fast(x, x):
+        # patch embed, transformer and the x4 trilinear add on HIP (csrc/transformer.hip), decided here, before
+        # the fork: the add needs conv1_up(c1) in x's shape, which it has whenever x's axes are even (a
+        # stride-2 conv leaves ceil(n / 2), the deconv doubles that) -- and _dt_fast takes multiples of 4 only
+        dt_fast = self._dt_fast(x)
+        if dt_fast:
             # the disparity transformer branch (patch embed + 4 encoder layers, ~0.45 ms at cfg2, a few
-            # hundred waves) reads only x: it runs on a side stream beside conv1 .. conv1_up
+            # hundred waves) reads only x: it runs on a side stream beside conv1 .. conv1_up, or with
+            # update.OVERLAP off on the calling stream, in order
             main = streams.current(x.device)
-            dt_s = streams.side(x.device, streams.BRANCH)
+            dt_s = streams.side(x.device, streams.BRANCH) if _update.OVERLAP else main
             with streams.fork(dt_s, main):
                 scale, shift = self._patch_fold()
                 t = self.atts["4"](ops.dt_patch_embed(_sub._f32(x), self.conv_patch[0].weight.float(), scale, shift))
@@ -153,26 +157,19 @@ class hourglass(nn.Module):
             c2 = self.feature_att_up_16(self.agg_0(torch.cat((self.conv3_up(c3), c2), dim=1)), features[2])
             c1 = self.feature_att_up_8(self.agg_1(torch.cat((self.conv2_up(c2), c1), dim=1)), features[1])
         conv = self.conv1_up(c1)
-        if dt_s is not None and tuple(conv.shape) == tuple(x.shape):
+        if dt_fast:
             streams.join(main, dt_s, t)
-            return self.conv_out(ops.upsample4_add_(conv.float().contiguous(), t))
-        if dt_s is not None:
-            streams.join(main, dt_s)
-        if self._dt_fast(x, conv):
-            # patch embed, transformer and the x4 trilinear add on HIP (csrc/transformer.hip)
-            scale, shift = self._patch_fold()
-            t = self.atts["4"](ops.dt_patch_embed(_sub._f32(x), self.conv_patch[0].weight.float(), scale, shift))
             return self.conv_out(ops.upsample4_add_(conv.float().contiguous(), t))
         t = self.atts["4"](self.conv_patch(x))
         conv = conv + F.interpolate(t, scale_factor=4, mode="trilinear", align_corners=False)
         return self.conv_out(conv)
 
-    def _dt_fast(self, x, conv) -> bool:
+    def _dt_fast(self, x) -> bool:
         pc, bn = self.conv_patch[0], self.conv_patch[1]
-        return (_sub._hip(x) and conv.dtype in _sub.HIP_DTYPES and not self.training and _sub.DT_FAST
+        return (_sub._hip(x) and not self.training and _sub.DT_FAST
                 and pc.groups == pc.in_channels == pc.out_channels and pc.kernel_size == (4, 4, 4)
                 and pc.stride == (4, 4, 4) and pc.padding == (0, 0, 0) and bn.track_running_stats
-                and all(n % 4 == 0 for n in x.shape[2:]) and tuple(conv.shape) == tuple(x.shape))
+                and all(n % 4 == 0 for n in x.shape[2:]))
 
     def _patch_fold(self):
         """conv_patch bias + eval BatchNorm3d as per-channel (scale, shift), cached per version."""
@@ -348,61 +345,50 @@ class FoundationStereo(nn.Module):
         md = self.args.get("mixed_dtype", "float16")
         with autocast(mp, md):
             features_left, features_right, vit_feat = self._backbone(image1, image2)
-            ctx_s = None
-            ctx_overlap = _update.OVERLAP and image1.is_cuda and not torch.is_grad_enabled()
-            corr_pyr = None
-            if ctx_overlap:
-                # the two HBM / MFMA kernels the north star measures run ALONE on the chip, before any
-                # side stream forks: the cost-volume build, then the all-pairs correlation pyramid (it
-                # needs only the features; the side streams' convs used to stretch it 10x beside the
-                # classifier).  ~70 us on the main stream; the side streams are far off the critical path.
-                # (The volume pyramid follows the hourglass on the main stream, before the classifier.)
-                vol = self.build_stem_volume(features_left[0], features_right[0])
-                corr_pyr = Combined_Geo_Encoding_Volume.corr_pyramid(features_left[0].float(),
-                                                                     features_right[0].float(),
-                                                                     self.args.corr_levels)
-                # stem_2 + context net + CAM / SAM read only the images and vit_feat: a side stream
-                # runs them beside the volume build and the 3D filtering (joined before the loop)
-                main = streams.current(image1.device)
-                ctx_s = streams.side(image1.device, streams.MOTION)
-                with streams.fork(ctx_s, main):
-                    stem_2x, net_list, inp_list, att = self._context(image1, vit_feat)
-                    ctx_pre = self.update_block.context_pre(inp_list)
-            else:
+            # the two HBM / MFMA kernels the north star measures run ALONE on the chip, before any
+            # side stream forks: the cost-volume build, then the all-pairs correlation pyramid (it
+            # needs only the features; the side streams' convs used to stretch it 10x beside the
+            # classifier).  ~70 us on the main stream; the side streams are far off the critical path.
+            # With grad enabled the geometry volume builds the pyramid itself, as it always has.
+            vol = self.build_stem_volume(features_left[0], features_right[0])
+            hip = image1.is_cuda and not torch.is_grad_enabled()
+            corr_pyr = Combined_Geo_Encoding_Volume.corr_pyramid(
+                features_left[0].float(), features_right[0].float(), self.args.corr_levels) if hip else None
+            # the side streams of what follows, or the main stream itself (streams.fork / join then run it
+            # in order): the context on the motion stream, the gates on the branch stream
+            ctx_overlap = _update.OVERLAP and hip
+            main = streams.current(image1.device)
+            ctx_s = streams.side(image1.device, streams.MOTION) if ctx_overlap else main
+            g_s = streams.side(image1.device, streams.BRANCH) if ctx_overlap else main
+            # stem_2 + context net + CAM / SAM read only the images and vit_feat: beside the 3D filtering,
+            # joined before the loop.  ctx_pre also where only update_block.forward will run, which does
+            # not take it
+            with streams.fork(ctx_s, main):
                 stem_2x, net_list, inp_list, att = self._context(image1, vit_feat)
                 ctx_pre = self.update_block.context_pre(inp_list)
-            fuse = _sub.FATT_FUSE and not self.training
-            gates = None
-            if fuse and ctx_s is not None:
-                # the six FeatureAtt gates (2D 1x1 convs on the features) on a side stream, ready long
-                # before the volume convs that apply them; an event joins only them
-                g_s = streams.side(image1.device, streams.BRANCH)
+            if _sub.FATT_FUSE and not self.training:
+                # the six FeatureAtt gates (2D 1x1 convs on the features), ready long before the volume
+                # convs that apply them; an event joins only them
                 with streams.fork(g_s, main):
                     gates = (self.corr_feature_att.logits(features_left[0]),) + \
                         self.cost_agg.gate_logits(features_left)
                     g_ev = streams.record(g_s)
-            if not ctx_overlap:
-                vol = self.build_stem_volume(features_left[0], features_right[0])
-            if fuse:
                 # corr_feature_att's sigmoid(gate) * vol in the last ResNet block's epilogue; the gates
                 # are joined right before it (~1 ms of volume convs after the fork)
                 for m in list(self.corr_stem)[1:-1]:
                     vol = m(vol)
-                if gates is not None:
-                    streams.join(main, g_s, *gates, event=g_ev)
-                g0 = gates[0] if gates is not None else self.corr_feature_att.logits(features_left[0])
-                vol = self.corr_stem[-1](vol, fatt=g0)
+                streams.join(main, g_s, *gates, event=g_ev)
+                vol = self.corr_stem[-1](vol, fatt=gates[0])
+                vol = self.cost_agg(vol, features_left, gates=gates[1:])
             else:
                 vol = self.corr_feature_att(self.corr_stem[1:](vol), features_left[0])
-            vol = self.cost_agg(vol, features_left, gates=None if gates is None else gates[1:])
-            geo_fn = None
-            if corr_pyr is not None:
-                # the volume pyramid (HBM-bound) on the main stream right after the hourglass, before the
-                # classifier's convs start: the gate and disparity-transformer branches joined inside the
-                # hourglass and the context stream (~1/10 of the hourglass's work) has long finished
-                geo_fn = Combined_Geo_Encoding_Volume(features_left[0].float(), features_right[0].float(),
-                                                      vol.float(), num_levels=self.args.corr_levels, dx=self.dx,
-                                                      init_corr_pyramid=corr_pyr)
+                vol = self.cost_agg(vol, features_left)
+            # the volume pyramid (HBM-bound) on the main stream right after the hourglass, before the
+            # classifier's convs start: the gate and disparity-transformer branches joined inside the
+            # hourglass and the context stream (~1/10 of the hourglass's work) has long finished
+            geo_fn = Combined_Geo_Encoding_Volume(features_left[0].float(), features_right[0].float(), vol.float(),
+                                                  num_levels=self.args.corr_levels, dx=self.dx,
+                                                  init_corr_pyramid=corr_pyr)
             if init_disp is None or self.keep_logits:
                 cl = self.classifier
                 head = cl[2]   # Conv3d(14, 1, 7, padding=3): direct gfx950 kernel (MIOpen: ~1 TFLOP/s here)
@@ -412,12 +398,8 @@ class FoundationStereo(nn.Module):
                     self.last_logits = logits
                 if init_disp is None:      # a given one stays (run_hierachical's second pass)
                     init_disp = ops.softmax_regression(logits)
-            if ctx_s is not None:
-                streams.join(main, ctx_s, stem_2x, *net_list, *inp_list, *att, *(ctx_pre or ()))
+            streams.join(main, ctx_s, stem_2x, *net_list, *inp_list, *att, *(ctx_pre or ()))
 
-        if geo_fn is None:
-            geo_fn = Combined_Geo_Encoding_Volume(features_left[0].float(), features_right[0].float(), vol.float(),
-                                                  num_levels=self.args.corr_levels, dx=self.dx)
         disp = init_disp.float()
         disp_preds = []
         disp_up = None

@@ -15,7 +15,9 @@ from . import ops
 #               branch; the mask head of forward_overlapped
 #   PIPELINE 3  gru16 / gru08 one iteration ahead (run_pipelined)
 # A caller forks work with ``with fork(side, origin):`` and takes it back with ``join(origin, side, *tensors)``;
-# ``on(stream)`` enqueues behind what the stream already holds, without a wait.
+# ``on(stream)`` enqueues behind what the stream already holds, without a wait.  Whether work leaves the origin is
+# the caller's choice of ``side``: a call site writes its sequence once, forked, and passes the origin itself as
+# the side stream to run it in order (update.OVERLAP or PIPE_BRANCH off, MOTION_ON_MAIN): fork and join then do nothing.
 MOTION, BRANCH, PIPELINE = 0, 1, 3
 NAMES = {MOTION: "motion", BRANCH: "branch", PIPELINE: "pipeline"}
 
@@ -135,14 +137,20 @@ def wait(waiter, waited, event=None):
 
 @contextlib.contextmanager
 def fork(side, origin):
-    """Context: ``side`` waits for ``origin`` and is the current stream."""
+    """Context: ``side`` waits for ``origin`` and is the current stream; ``side`` the origin itself: in order."""
+    if _skey(side) == _skey(origin):
+        yield
+        return
     wait(side, origin)
     with on(side):
         yield
 
 
 def join(origin, side, *tensors, event=None):
-    """``origin`` waits for ``side`` (up to ``event`` when given) and takes over ``tensors`` made there."""
+    """``origin`` waits for ``side`` (up to ``event`` when given) and takes over ``tensors`` made there;
+    nothing to do when ``side`` is the origin itself."""
+    if _skey(side) == _skey(origin):
+        return
     wait(origin, side, event)
     for t in tensors:
         keep(t, origin)

@@ -15,7 +15,7 @@ own kernels: ``convd1`` (1 -> 64, + ReLU) on ``ops.conv2d_1in``, the depthwise
 ``dwconv`` on ``ops.dwconv2d``; ``pool2x`` is ``ops.pool2x`` and ``interp``
 ``ops.resize_bilinear``.  Under the reference's autocast the same HIP path runs
 (fp16 inputs cast up, fp32 compute); with grad enabled the module runs the plain
-torch path (``CONV_ENGINE = "miopen"`` forces it, for A/B).
+torch path (``CONV_ENGINE = "miopen"`` forces it: bench.py's ``--conv-engine``).
 """
 from __future__ import annotations
 
@@ -32,12 +32,15 @@ from .submodule import EdgeNextConvEncoder, _cached, _f32, _hip
 #   CONV_ENGINE     "miopen" forces the torch path (bench.py --conv-engine)
 #   OVERLAP         side streams for the motion path, the GRU small branches, the mask head and the gru16 /
 #                   gru08 pipeline (FSMI_OVERLAP; bench.py).  The streams, and every fork / join / wait
-#                   between them, are streams.py's; whether a SelectiveConvGRU forks its small branch is
-#                   its caller's ``fork_small`` argument
+#                   between them, are streams.py's.  No knob here picks between two copies of a sequence:
+#                   each schedule is written once, forked, and a knob only picks the stream a fork goes to --
+#                   the slot's side stream, or the calling stream itself, on which streams.fork / join do
+#                   nothing and the same sequence runs in order.  Whether a SelectiveConvGRU forks its small
+#                   branch is its caller's ``fork_small`` argument
 #   PIPE_BRANCH     run_pipelined: gru04's small branch on its own stream, i.e. its ``fork_small``
 #                   (FSMI_PIPE_BRANCH; tests/test_gpu_capture_fork.py)
-#   MOTION_ON_MAIN  run_pipelined: the motion path (lookup + encoder) on the main stream instead of the
-#                   motion stream (FSMI_MOTION_ON_MAIN; tests/test_gpu_capture_fork.py)
+#   MOTION_ON_MAIN  run_pipelined: the motion path (lookup + encoder) forks to the main stream, i.e. stays on
+#                   it, instead of the motion stream (FSMI_MOTION_ON_MAIN; tests/test_gpu_capture_fork.py)
 #   CTX_PRE         SelectiveConvGRU.conv0's context segment convolved once per forward (context_pre);
 #                   False: every iteration (tests/test_gpu_ctx_pre.py, test_gpu_range.py set the attribute)
 #   COUT1           DispHead's last conv (128 -> 1) on its own fp32 kernel (ops.conv3x3_cout1); False: the
@@ -330,18 +333,14 @@ class SelectiveConvGRU(nn.Module):
                 pk, b, z, rh = branch(sg, "blend_small")
                 ops.conv2d_gate([rh, xc], pk, b, "blend_small", h=h, z=z, att=att, out=out)
 
-            if OVERLAP and fork_small:
-                # small (1x1) branch on a side stream beside the large branch's zr conv; the
-                # large blend adds into ``out`` after the small blend has written it
-                main = streams.current(h.device)
-                side = streams.side(h.device, streams.BRANCH)
-                with streams.fork(side, main):
-                    small()
-                pk, b, z, rh = branch(self.large_gru, "blend_large")
-                streams.join(main, side)
-            else:
+            # small (1x1) branch on a side stream beside the large branch's zr conv; the
+            # large blend adds into ``out`` after the small blend has written it
+            main = streams.current(h.device)
+            side = streams.side(h.device, streams.BRANCH) if OVERLAP and fork_small else main
+            with streams.fork(side, main):
                 small()
-                pk, b, z, rh = branch(self.large_gru, "blend_large")
+            pk, b, z, rh = branch(self.large_gru, "blend_large")
+            streams.join(main, side)
             ops.conv2d_gate([rh, xc], pk, b, "blend_large", h=h, z=z, att=att, out=out)
             return out
         x = torch.cat(x, dim=1) if len(x) > 1 else x[0]
@@ -375,8 +374,9 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
                                   nn.Conv2d(64, 32, 3, padding=1), nn.ReLU(inplace=True))
 
     def forward(self, net, inp, corr, disp, att):
-        if _fast(corr):
-            return self._forward_fast(_f32s(net), _f32s(inp), _f32(corr), _f32(disp), _f32s(att))
+        if _fast(corr):     # one iteration in order on the calling stream; conv0 convolves the whole cat (pre=None)
+            corr = _f32(corr)
+            return self._iteration(_f32s(net), _f32s(inp), lambda d: corr, _f32(disp), _f32s(att), None, False)
         n = self.args.n_gru_layers
         if n == 3:
             net[2] = self.gru16(att[2], net[2], inp[2], pool2x(net[1]))
@@ -404,38 +404,39 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
     def forward_overlapped(self, net, inp, geo_fn, disp, att, pre=None):
         """``forward(net, inp, geo_fn(disp), disp, att)`` with the motion path -- the lookup and
         the motion encoder, which depend only on ``disp`` -- on a side stream, concurrently with
-        gru16 / gru08 (small 1/16 and 1/8 maps that leave most CUs idle).  Joined before gru04.
+        gru16 / gru08 (small 1/16 and 1/8 maps that leave most CUs idle), joined before gru04, and the mask
+        head on the branch stream beside the disparity head (both read net[0] only).  With ``OVERLAP`` off
+        the same sequence runs on the calling stream.  ``pre``: ``context_pre(inp)`` or None."""
+        return self._iteration(net, inp, geo_fn, disp, att, pre, OVERLAP)
+
+    def _iteration(self, net, inp, geo_fn, disp, att, pre, overlap):
+        """One refinement iteration on the HIP path; ``overlap``: the motion and branch streams, else every
+        stream is the calling one (streams.fork / join then run the sequence in order).
         Cross-stream buffers (``enc``) are allocated on the calling stream and ``disp`` is only
         released by the caller after the join, so the caching allocator never recycles memory a
         pending side-stream kernel still reads.  Captures into a hipGraph as a fork/join."""
-        main = streams.current(disp.device)
-        s_mot, s_br = streams.side(disp.device, streams.MOTION), streams.side(disp.device, streams.BRANCH)
+        dev, n = disp.device, self.args.n_gru_layers
+        main = streams.current(dev)
+        s_mot = streams.side(dev, streams.MOTION) if overlap else main
+        s_br = streams.side(dev, streams.BRANCH) if overlap else main
         B, _, H, W = disp.shape
         enc = disp.new_empty(B, self.encoder.conv.out_channels + 1, H, W)
         with streams.fork(s_mot, main):
             self.encoder.motion_into(disp, geo_fn, enc)
         p0, p1, p2 = (list(pre) + [None] * 3)[:3] if pre is not None else (None, None, None)
-        self._coarse_grus(net, inp, att, p1, p2)
+        if n == 3:
+            net[2] = self.gru16(att[2], net[2], inp[2], pool2x(net[1]), pre=p2)
+        if n >= 2:
+            xs = [pool2x(net[0])] + ([interp(net[2], net[1])] if n > 2 else [])
+            net[1] = self.gru08(att[1], net[1], inp[1], *xs, pre=p1)
         streams.join(main, s_mot)
-        if self.args.n_gru_layers > 1:
+        if n > 1:       # motion = cat([inp[0], enc]) stays two segments of gru04.conv0's input
             net[0] = self.gru04(att[0], net[0], inp[0], enc, interp(net[1], net[0]), pre=p0)
-        # mask head beside the disparity head (both read net[0] only)
         with streams.fork(s_br, main):
             mask = self._mask_head(net[0])
         delta_disp = self.disp_head(net[0])
         streams.join(main, s_br)
         return net, mask, delta_disp
-
-    def _coarse_grus(self, net, inp, att, p1=None, p2=None):
-        """gru16, then gru08, of one iteration (HIP path), written into ``net``; ``p1`` / ``p2``: their context_pre."""
-        n = self.args.n_gru_layers
-        if n == 3:
-            net[2] = self.gru16(att[2], net[2], inp[2], pool2x(net[1]), pre=p2)
-        if n >= 2:
-            if n > 2:
-                net[1] = self.gru08(att[1], net[1], inp[1], pool2x(net[0]), interp(net[2], net[1]), pre=p1)
-            else:
-                net[1] = self.gru08(att[1], net[1], inp[1], pool2x(net[0]), pre=p1)
 
     def _mask_head(self, n0):
         """0.25 * mask(n0) on the HIP path (the scale in the last conv's epilogue)."""
@@ -460,7 +461,8 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
         conv0 parts per level) or None."""
         dev = disp.device
         main = streams.current(dev)
-        s_mot, s_gru = streams.side(dev, streams.MOTION), streams.side(dev, streams.PIPELINE)
+        s_mask, s_gru = streams.side(dev, streams.MOTION), streams.side(dev, streams.PIPELINE)
+        s_mot = main if MOTION_ON_MAIN else s_mask       # the motion path's stream; the mask head keeps s_mask
         n0, n1, n2 = net
         p0, p1, p2 = pre if pre is not None else (None, None, None)
         B, _, H, W = disp.shape
@@ -477,14 +479,10 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
         enc[:, nc:].copy_(disp)
         disp = enc[:, nc:]
         for t in range(iters):
-            if MOTION_ON_MAIN:
+            with streams.fork(s_mot, main):
                 self.encoder.motion_into(disp, geo_fn, enc)
-            else:
-                with streams.fork(s_mot, main):
-                    self.encoder.motion_into(disp, geo_fn, enc)
             streams.join(main, s_gru)                     # gru08(t): enqueued last on s_gru so far
-            if not MOTION_ON_MAIN:
-                streams.join(main, s_mot)                 # motion(t)
+            streams.join(main, s_mot)                     # motion(t)
             if t + 1 < iters:
                 with streams.on(s_gru):                  # gru16(t+1), beside gru04(t): behind gru08(t), no wait
                     n2 = self.gru16(att[2], n2, inp[2], pool2x(n1), pre=p2, fork_small=False)
@@ -496,28 +494,16 @@ class BasicSelectiveMultiUpdateBlock(nn.Module):
             if t + 1 < iters:
                 with streams.fork(s_gru, main):          # gru08(t+1) after gru04(t), beside the heads + motion(t+1)
                     n1 = self.gru08(att[1], n1, inp[1], pool2x(n0), up2, pre=p1, fork_small=False)
-            if t + 1 == iters:
-                # test mode upsamples only the last iteration's disparity: the reference computes the
-                # mask head every iteration and discards all but the last (core/foundation_stereo.py:243-244)
-                with streams.fork(s_mot, main):
-                    mask = self._mask_head(n0)
-            if t + 1 < iters:
                 enc = disp.new_empty(B, nc + 1, H, W)
                 self.disp_head(n0, res=disp, out=enc, co0=nc)
                 disp = enc[:, nc:]
-            else:
-                disp = self.disp_head(n0, res=disp)
-            if not MOTION_ON_MAIN or t + 1 == iters:
                 streams.join(main, s_mot)
+            else:
+                # test mode upsamples only the last iteration's disparity: the reference computes the
+                # mask head every iteration and discards all but the last (core/foundation_stereo.py:243-244)
+                with streams.fork(s_mask, main):
+                    mask = self._mask_head(n0)
+                disp = self.disp_head(n0, res=disp)
+                streams.join(main, s_mask)
         streams.join(main, s_gru)
         return [n0, n1, n2], mask, disp
-
-    def _forward_fast(self, net, inp, corr, disp, att):
-        self._coarse_grus(net, inp, att)
-        B, _, H, W = corr.shape
-        enc = self.encoder.encode_into(disp, corr, corr.new_empty(B, self.encoder.conv.out_channels + 1, H, W))
-        # motion = cat([inp[0], enc]) stays two segments of gru04.conv0's input
-        if self.args.n_gru_layers > 1:
-            net[0] = self.gru04(att[0], net[0], inp[0], enc, interp(net[1], net[0]))
-        delta_disp = self.disp_head(net[0])
-        return net, self._mask_head(net[0]), delta_disp

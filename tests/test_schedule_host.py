@@ -15,8 +15,15 @@ CPU tensors.  A value is a region of a tensor's storage, so the disparity the he
   (d) every wait has the caller's stream on one side ("fork only from the origin").
 
 Two negative controls drop one wait each and must make (a) report a race.
+
+Every call site writes its sequence once and picks the streams; with the side stream the caller's own,
+``streams.fork`` / ``join`` (the real ones run here) do nothing.  The in-order variants -- ``OVERLAP`` off, the HIP
+arm of ``forward``, ``fork_small=False`` -- must log every op on the caller's stream, issue no wait, and do the
+same work as the forked run: the same multiset of (op, regions read, regions written), ``dataflow``.
 """
+import collections
 import contextlib
+import hashlib
 import types
 
 import pytest
@@ -122,6 +129,29 @@ class Sched:
             assert self.main in (w, d), f"{w} waits on {d}"                            # (d)
 
 
+def dataflow(sc):
+    """The log as a multiset of (op, regions read, regions written).  A storage is named by the op that first
+    wrote it and what that op read, not by its address: the same in two runs on the same inputs whatever the
+    streams and the enqueue order of independent work."""
+    ids, out = {}, collections.Counter()
+    for name, _, _, reads, writes in sc.ops:
+        r = tuple((ids.get(p, "unwritten"), lo, hi) for p, lo, hi in reads)
+        for k, (p, lo, hi) in enumerate(writes):
+            ids.setdefault(p, hashlib.sha1(repr((name, r, k, hi - lo)).encode()).hexdigest()[:16])
+        out[(name, r, tuple((ids[p], lo, hi) for p, lo, hi in writes))] += 1
+    return out
+
+
+def assert_in_order(sc, forked):
+    """``sc`` ran everything on the caller's stream without a wait, and did the work of ``forked``."""
+    assert {s.name for _, s, _, _, _ in sc.ops} == {"main"}
+    assert sc.waits == [] and sc.seen == {}
+    assert sc.races() == []
+    assert forked.waits and {s.name for _, s, _, _, _ in forked.ops} > {"main"}      # the control did fork
+    assert dataflow(sc) == dataflow(forked)
+    assert sum(dataflow(sc).values()) == len(sc.ops) == len(forked.ops)
+
+
 def seg_tensors(segs):
     return [s[0] if isinstance(s, tuple) else s for s in segs]
 
@@ -170,7 +200,7 @@ def make_block(sc, n_gru_layers):
         return g
 
     def motion_into(disp, geo_fn, out):
-        geo = sc.rec("lookup", [disp], shape=disp.shape)
+        geo = geo_fn(disp) if geo_fn is not None else sc.rec("lookup", [disp], shape=disp.shape)
         tail = out[:, NC:]
         sc.rec("encoder", [geo, disp], [out[:, :NC]] + ([tail] if tail.data_ptr() != disp.data_ptr() else []))
         return out
@@ -232,6 +262,48 @@ def test_forward_overlapped(sched, n_gru_layers):
     sc.check()
     assert {s.name for _, s, _, _, _ in sc.ops} == {"main", "motion", "branch"}
     assert sum(n == "blend_small" for n, _, _, _, _ in sc.ops) == 2 * n_gru_layers
+
+
+def iterate(sc, n_gru_layers, hip_forward):
+    """Two iterations of ``forward_overlapped``, or of ``forward``'s HIP arm on a looked-up ``corr``."""
+    blk = make_block(sc, n_gru_layers)
+    net, inp, att, _, disp = inputs(sc, n_gru_layers)
+    for _ in range(2):
+        if hip_forward:
+            net, mask, delta = blk.forward(net, inp, sc.rec("lookup", [disp], shape=disp.shape), disp, att)
+        else:
+            net, mask, delta = blk.forward_overlapped(net, inp, None, disp, att)
+        disp = sc.rec("add", [disp, delta], shape=disp.shape)
+        sc.rec("upsample", [disp, mask])
+    sc.check()
+    return sc
+
+
+@pytest.mark.parametrize("hip_forward", [False, True])
+@pytest.mark.parametrize("n_gru_layers", [3, 2])
+def test_iteration_in_order(sched, n_gru_layers, hip_forward):
+    """``OVERLAP`` off: ``forward_overlapped`` and the HIP arm of ``forward`` run one body on the caller's stream."""
+    forked = iterate(sched(), n_gru_layers, hip_forward)
+    sc = iterate(sched(OVERLAP=False), n_gru_layers, hip_forward)
+    assert_in_order(sc, forked)
+    # forward keeps its streams to itself also with OVERLAP on: only the GRUs' small branches fork
+    assert {s.name for n, s, _, _, _ in forked.ops if s.name != "main"} == (
+        {"branch"} if hip_forward else {"motion", "branch"})
+    assert {n for n, s, _, _, _ in forked.ops if s.name == "branch"} == (
+        {"gate_zr", "blend_small"} | (set() if hip_forward else {"conv2d"}))
+
+
+def test_selective_gru_fork_small(sched):
+    """``fork_small=False`` (a caller on a side stream) against the forked small branch."""
+    def run(sc, fork_small):
+        gru = make_block(sc, 3).gru04
+        (h,), (x0,), (att,), (pre,), _ = inputs(sc, 1)
+        x1 = sc.rec("motion", shape=h.shape)
+        out = gru(att, h, x0, x1, pre=pre, fork_small=fork_small)
+        sc.rec("reader", [out])
+        sc.check()
+        return sc
+    assert_in_order(run(sched(), False), run(sched(), True))
 
 
 # negative controls: with one wait of the schedule not issued, (a) must report the race it guarded
