@@ -126,7 +126,8 @@ __global__ __launch_bounds__(256) void conv_depth_kernel(HaloArgs a) {
       // the exact power of two -- every plane keeps ~22 bits relative to its OWN maximum (a block
       // spans 31 planes of a cost volume, whose magnitudes differ by decades along the disparity
       // axis); the exponent never climbs more than 60 above the block's smallest, so accumulators
-      // of earlier large planes stay far inside fp32 (< 2^100)
+      // of earlier large planes stay far inside fp32 (< 2^100).  A different policy from the halo
+      // tiles' BlockExp (conv_halo.h), which only ever lowers the exponent: kept separate on purpose
       const int fit = __builtin_amdgcn_readfirstlane(chunk_exp(bm));
       if (fit != kNoExp && (fit < sx || (sx != kNoExp && fit > sx + 8))) {
         int se = __builtin_amdgcn_readfirstlane(chunk_exp<kHeadroom1>(bm));

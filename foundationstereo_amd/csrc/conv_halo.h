@@ -22,7 +22,10 @@
 // instantiates it from the tile table (conv_tiles.h); each (kernel size, 2D / volume) pair
 // compiles in its own translation unit (conv_halo_k{1,2,3}_{2d,3d}.hip and conv_halo_s2_3d.hip,
 // built in parallel), and conv_halo_x3.hip holds the host side (tile / split-K policy, C ABI) and
-// the reduce pass.
+// the reduce pass.  The "shared pieces" section holds what every conv kernel (conv_pw.hip and
+// conv_depth.hip too) is built from, each once: staging (HaloStage, load_chunk), the block exponent
+// (BlockExp), zero_acc / mma3, the packed-weight offset (weight_base).  Each kernel keeps its own
+// weight loader and tap loop: measured, sharing those cost the register-weight tiles 4-6 %.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -580,6 +583,14 @@ struct TileCoord {
   int m0, b, d0, r0, c0, split;
 };
 
+// chunk cc of tile tc into hs's registers: 2D maps, channel chunk cc; volumes, cc = (kd, channel
+// chunk) with kd major, read from input plane STR * d0 + kd - PDD (+ the transposed-conv phase shift)
+template <bool D3, int STR, typename HS>
+__device__ __forceinline__ void load_chunk(HS& hs, const HaloArgs& a, const TileCoord& tc, int cc, int nck) {
+  if constexpr (D3) hs.load(a, tc.b, cc % nck, STR * tc.d0 + cc / nck - a.PDD + a.sd);
+  else hs.load(a, tc.b, cc);
+}
+
 // ---- range-safe split: a block exponent per 32-channel chunk
 // fp16 hi / lo halves hold x to ~22 bits only while |x| < 65504 and x's low half stays normal
 // (|x| >~ 0.1).  Before a chunk is split, the block takes the largest |x| of the chunk (wave
@@ -645,6 +656,52 @@ __device__ __forceinline__ void rescale_acc(f32x16 (&acc)[TM][TN], float f) {
     for (int j = 0; j < TN; ++j) acc[i][j] *= f;
 }
 
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// The block (K group) exponent of one run of chunks, range mode RM (range_mode above).  Per chunk
+// that wants_max(): publish() the staged chunk's largest |x|, a barrier of the kernel's own (each
+// kernel has its own schedule), then settle().
+template <int RM>
+struct BlockExp {
+  static_assert(RM == 1 || RM == 2, "range mode 1 (volumes) or 2 (2D maps)");
+  int sx = kNoExp;                 // see chunk_exp
+  bool ovf = false;
+  // mode 1: every chunk.  Mode 2: until the first chunk holding a nonzero value (an all-zero first
+  // chunk would otherwise leave scale 1 and drop small later values to fp16 subnormals)
+  __device__ __forceinline__ bool wants_max() const { return RM == 1 || sx == kNoExp; }
+  // this thread's max |x| of the chunk -> the wave's slot of red[4]
+  __device__ __forceinline__ void publish(float m, float* red, int lane, int wave) const {
+    const float wmax = wave_max(m);
+    if (lane == 0) red[wave] = wmax;           // wave-uniform (SGPR)
+  }
+  template <int TM, int TN>
+  __device__ __forceinline__ void settle(f32x16 (&acc)[TM][TN], const float* red) {
+    if constexpr (RM == 1) {
+      const float bm = red4_max(red);
+      ovf |= !(bm <= 3.4e38f);                  // an inf input (NaN is ignored by the max)
+      // rescale only when the chunk does not fit the current exponent; then re-aim with headroom
+      // so that the chunks after it rarely trigger another rescale
+      if (__builtin_amdgcn_readfirstlane(chunk_exp(bm)) < sx) {
+        const int se = __builtin_amdgcn_readfirstlane(chunk_exp<kHeadroom1>(bm));     // block-uniform
+        if (sx != kNoExp) rescale_acc<TM, TN>(acc, exp2i(se - sx));
+        sx = se;
+      }
+    } else if (sx == kNoExp) {
+      sx = __builtin_amdgcn_readfirstlane(chunk_exp<kRangeHeadroom>(red4_max(red)));
+    }
+  }
+  __device__ __forceinline__ float scale() const { return exp2i(sx == kNoExp ? 0 : sx); }   // of the split
+  __device__ __forceinline__ float inv() const { return exp2i(sx == kNoExp ? 0 : -sx); }    // of the epilogue
+};
+
 // Tile t (cout tile = t / npix, pixel tile = t % npix; D3: depth fastest) -> coordinates
 template <int BM, int TR, bool D3>
 __device__ __forceinline__ TileCoord tile_coord(const HaloArgs& a, int ctile, int ptile) {
@@ -696,6 +753,14 @@ __device__ __forceinline__ void mma3(f32x16 (&acc)[TM][TN], const half8 (&ah)[TM
       }
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
     }
+}
+
+// element offset of the packed weight slice [CoutP][32] of tap `tap` (of NTAP) and chunk cc: 2D
+// [tap][chunk]; volumes, cc = (kd, channel chunk) with kd major, [kd][tap][chunk]
+template <bool D3, int NTAP>
+__device__ __forceinline__ size_t weight_base(const HaloArgs& a, int nck, int cc, int tap) {
+  return (D3 ? static_cast<size_t>((cc / nck) * NTAP + tap) * nck + cc % nck : static_cast<size_t>(tap) * nck + cc) *
+         a.CoutP * HKC;
 }
 
 // The block's per-cout epilogue coefficients, staged into LDS at the start of the kernel (their
@@ -827,8 +892,7 @@ __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
   const bool w_full = m0 + BM <= a.CoutP;          // block-uniform: only the last cout tile is ragged
   uint4 rwh[W_PER_T], rwl[W_PER_T];
   auto load_w = [&](int cc, int tap) {
-    const size_t base = D3 ? (static_cast<size_t>((cc / nck) * NTAP + tap) * nck + cc % nck) * a.CoutP * HKC
-                           : (static_cast<size_t>(tap) * nck + cc) * a.CoutP * HKC;
+    const size_t base = weight_base<D3, NTAP>(a, nck, cc, tap);
     const _Float16* ph = a.whi + base;
     const _Float16* pl = a.wlo + base;
     if (w_full) {
@@ -866,47 +930,21 @@ __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
   hs.init(a, tid, tc.r0, tc.c0);
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   // split-K: this block reduces chunks [cc_begin, cc_end)
   const int cc_begin = tc.split * a.kpc;
   const int cc_end = min(nq, cc_begin + a.kpc);
   int step = 0;
   load_w(cc_begin, 0);
-  if constexpr (D3) hs.load(a, tc.b, cc_begin % nck, tc.d0 + cc_begin / nck - a.PDD + a.sd);
-  else hs.load(a, tc.b, cc_begin);
-  int sx = kNoExp;                 // block exponent of the split (see chunk_exp)
-  bool ovf = false;
-  constexpr bool m1 = RM == 1;     // per-chunk exponent (mode 1)
+  load_chunk<D3, 1>(hs, a, tc, cc_begin, nck);
+  BlockExp<RM> bx;                 // block exponent of the split
   for (int cc = cc_begin; cc < cc_end; ++cc) {
-    if (m1 || (RM == 2 && sx == kNoExp)) {
-      const float m = wave_max(hs.absmax());
-      if (lane == 0) red[wave] = m;           // m is wave-uniform (SGPR)
-    }
+    if (bx.wants_max()) bx.publish(hs.absmax(), red, lane, wave);
     __syncthreads();               // every wave is done with the previous chunk's halo; maxima visible
-    if (m1) {
-      const float bm = red4_max(red);
-      ovf |= !(bm <= 3.4e38f);                  // an inf input (NaN is ignored by the max)
-      // rescale only when the chunk does not fit the current exponent; then re-aim with headroom
-      // so that the chunks after it rarely trigger another rescale
-      if (__builtin_amdgcn_readfirstlane(chunk_exp(bm)) < sx) {
-        const int se = __builtin_amdgcn_readfirstlane(chunk_exp<kHeadroom1>(bm));     // block-uniform
-        if (sx != kNoExp) rescale_acc<TM, TN>(acc, exp2i(se - sx));
-        sx = se;
-      }
-    } else if (RM == 2 && sx == kNoExp) {       // first chunk with a nonzero value
-      sx = __builtin_amdgcn_readfirstlane(chunk_exp<kRangeHeadroom>(red4_max(red)));
-    }
-    hs.template store<RM>(Xh, Xl, tid, exp2i(sx == kNoExp ? 0 : sx), ovf);
-    if (cc + 1 < cc_end) {
-      if constexpr (D3) hs.load(a, tc.b, (cc + 1) % nck, tc.d0 + (cc + 1) / nck - a.PDD + a.sd);
-      else hs.load(a, tc.b, cc + 1);
-    }   // in flight during this chunk's taps
+    bx.settle(acc, red);
+    hs.template store<RM>(Xh, Xl, tid, bx.scale(), bx.ovf);
+    if (cc + 1 < cc_end) load_chunk<D3, 1>(hs, a, tc, cc + 1, nck);   // in flight during this chunk's taps
 #pragma unroll 1
     for (int tap = 0; tap < NTAP; ++tap, ++step) {
       const int buf = step & 1;
@@ -935,9 +973,8 @@ __global__ __launch_bounds__(256) void conv_halo_x3_kernel(HaloArgs a) {
       }
     }
   }
-  flag_overflow(a, ovf);
-  conv_epilogue<TM, TN, D3, D3 || KS == 2>(a, acc, exp2i(sx == kNoExp ? 0 : -sx), tc, wm, wn, lane, a.nsplit > 1,
-                                           ecoef.sb, ecoef.g);
+  flag_overflow(a, bx.ovf);
+  conv_epilogue<TM, TN, D3, D3 || KS == 2>(a, acc, bx.inv(), tc, wm, wn, lane, a.nsplit > 1, ecoef.sb, ecoef.g);
 }
 
 // -------------------------------------------------- register-weight tiles: weights in registers
@@ -985,8 +1022,7 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
     half8 wf[2][TM][2][2];         // [buffer][i][k half][hi, lo]
     auto load_wf = [&](auto buf_c, int cc, int tap) FSMI_HALO_INL {
       constexpr int buf = decltype(buf_c)::value;
-      const size_t base = D3 ? (static_cast<size_t>((cc / nck) * NTAP + tap) * nck + cc % nck) * a.CoutP * HKC
-                             : (static_cast<size_t>(tap) * nck + cc) * a.CoutP * HKC;
+      const size_t base = weight_base<D3, NTAP>(a, nck, cc, tap);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1002,12 +1038,7 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
     float* gred = red[grp];
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int c_first = cc_begin + grp;              // this group's chunks: c_first, c_first + KG, ...
     const int n_g = c_first < cc_end ? (cc_end - c_first + KG - 1) / KG : 0;
@@ -1059,46 +1090,24 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
         __builtin_amdgcn_sched_barrier(0);
       });
     };
-    int sx = kNoExp;               // block (group) exponent of the segment (see chunk_exp)
-    bool ovf = false;
-    constexpr bool m1 = RM == 1;     // per-chunk exponent (mode 1)
+    BlockExp<RM> bx;               // block (group) exponent of the segment
     // q-th chunk of this group (cc = c_first + KG q); both groups run the same number of stages
     // (barriers), a group past its last chunk idles through them
     auto stage = [&](int q) FSMI_HALO_INL {
       const int cc = c_first + KG * q;
       const bool valid = q < n_g;
-      // mode 2 fixes the exponent at the first chunk holding a nonzero value (an all-zero first
-      // chunk would otherwise leave scale 1 and drop small later values to fp16 subnormals)
-      if (valid && (m1 || (RM == 2 && sx == kNoExp))) {
-        const float m = wave_max(hs.absmax());
-        if (lane == 0) gred[wave] = m;          // m is wave-uniform (SGPR)
-      }
+      if (valid && bx.wants_max()) bx.publish(hs.absmax(), gred, lane, wave);
       __syncthreads();             // every wave is done with the previous chunk's halo; maxima visible
       if (valid) {
-        if (m1) {
-          const float bm = red4_max(gred);
-          ovf |= !(bm <= 3.4e38f);              // an inf input (NaN is ignored by the max)
-          // rescale only when the chunk does not fit the current exponent; then re-aim with headroom
-          if (__builtin_amdgcn_readfirstlane(chunk_exp(bm)) < sx) {
-            const int se = __builtin_amdgcn_readfirstlane(chunk_exp<kHeadroom1>(bm));   // group-uniform
-            if (sx != kNoExp) rescale_acc<TM, TN>(acc, exp2i(se - sx));
-            sx = se;
-          }
-        } else if (RM == 2 && sx == kNoExp) {
-          sx = __builtin_amdgcn_readfirstlane(chunk_exp<kRangeHeadroom>(red4_max(gred)));
-        }
-        hs.template store<RM>(gXh, gXl, tid, exp2i(sx == kNoExp ? 0 : sx), ovf);
-        if (cc + KG < cc_end) {
-          if constexpr (D3) hs.load(a, tc.b, (cc + KG) % nck, STR * tc.d0 + (cc + KG) / nck - a.PDD + a.sd);
-          else hs.load(a, tc.b, cc + KG);
-        }   // in flight during this chunk's taps
+        bx.settle(acc, gred);
+        hs.template store<RM>(gXh, gXl, tid, bx.scale(), bx.ovf);
+        if (cc + KG < cc_end) load_chunk<D3, STR>(hs, a, tc, cc + KG, nck);   // in flight during this chunk's taps
       }
       __syncthreads();
     };
     if (n_g > 0) {
       load_wf(std::integral_constant<int, 0>(), c_first, 0);
-      if constexpr (D3) hs.load(a, tc.b, c_first % nck, STR * tc.d0 + c_first / nck - a.PDD + a.sd);
-      else hs.load(a, tc.b, c_first);
+      load_chunk<D3, STR>(hs, a, tc, c_first, nck);
     }
     // chunks in pairs so every register-buffer index is static (parity 0, then 1)
     const int n_all = (cc_end - cc_begin + KG - 1) / KG;   // stages every group runs
@@ -1113,8 +1122,8 @@ __global__ __launch_bounds__(256 * KG) void conv_halo_wreg_kernel(HaloArgs a) {
       stage(q);
       if (q < n_g) chunk(std::integral_constant<int, 0>(), c_first + KG * q);
     }
-    flag_overflow(a, ovf);
-    float xinv = exp2i(sx == kNoExp ? 0 : -sx);
+    flag_overflow(a, bx.ovf);
+    float xinv = bx.inv();
     unsigned fown = ~0u;
     if constexpr (KG == 2) {
       // the other group's half of every fragment this group finishes, through LDS (the halo
@@ -1227,7 +1236,7 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
   half8 wf[2][TM][2][2];           // [buffer][i][k half][hi, lo]
   auto load_wf = [&](auto buf_c, int cc, int tap) FSMI_HALO_INL {
     constexpr int buf = decltype(buf_c)::value;
-    const size_t base = (static_cast<size_t>(tap) * nck + cc) * a.CoutP * HKC;
+    const size_t base = weight_base<false, NTAP>(a, nck, cc, tap);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1239,27 +1248,19 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
   HS hs;
   hs.init(a, tid, tc.r0, tc.c0);
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
-  int sx = kNoExp;
-  bool ovf = false;
-  auto scale = [&]() FSMI_HALO_INL { return exp2i(sx == kNoExp ? 0 : sx); };
-  auto fix_exponent = [&]() FSMI_HALO_INL {        // block-wide max of the registers' chunk -> sx
-    const float m = wave_max(hs.absmax());
-    if (lane == 0) red[wave] = m;
+  BlockExp<RM> bx;
+  auto fix_exponent = [&]() FSMI_HALO_INL {        // block-wide max of the registers' chunk -> bx
+    bx.publish(hs.absmax(), red, lane, wave);
     __syncthreads();
-    sx = __builtin_amdgcn_readfirstlane(chunk_exp<kRangeHeadroom>(red4_max(red)));
+    bx.settle(acc, red);
   };
   // prologue: chunk 0 -> buffer 0 (its max fixes the exponent), chunk 1 into registers
   load_wf(std::integral_constant<int, 0>(), c_first, 0);
   hs.load(a, tc.b, c_first);
   fix_exponent();
-  hs.template store<RM>(Xh[0], Xl[0], tid, scale(), ovf);
+  hs.template store<RM>(Xh[0], Xl[0], tid, bx.scale(), bx.ovf);
   if (n > 1) hs.load(a, tc.b, c_first + 1);
   __syncthreads();
 
@@ -1295,8 +1296,8 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
       if (tap == STAGE_TAP && q + 1 < n) {
         // next chunk: registers (loaded one chunk ago) -> fp16 hi / lo -> the other buffer, then the
         // chunk after it into the registers
-        if (sx == kNoExp) fix_exponent();   // every chunk so far all zero (uniform)
-        hs.template store<RM>(Xh[P ^ 1], Xl[P ^ 1], tid, scale(), ovf);
+        if (bx.wants_max()) fix_exponent();   // every chunk so far all zero (uniform)
+        hs.template store<RM>(Xh[P ^ 1], Xl[P ^ 1], tid, bx.scale(), bx.ovf);
         if (q + 2 < n) hs.load(a, tc.b, cc + 2);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1322,9 +1323,8 @@ __global__ __launch_bounds__(256) void conv_halo_pipe_kernel(HaloArgs a) {
     chunk(std::integral_constant<int, 1>(), q + 1);
   }
   if (q < n) chunk(std::integral_constant<int, 0>(), q);
-  flag_overflow(a, ovf);
-  conv_epilogue<TM, TN, false>(a, acc, exp2i(sx == kNoExp ? 0 : -sx), tc, wm, wn, lane, a.nsplit > 1,
-                                ecoef.sb, ecoef.g);
+  flag_overflow(a, bx.ovf);
+  conv_epilogue<TM, TN, false>(a, acc, bx.inv(), tc, wm, wn, lane, a.nsplit > 1, ecoef.sb, ecoef.g);
 }
 
 template <int KS, int BM, int TR, int WM, bool WREG, bool D3, int KG = 1, int STR = 1>

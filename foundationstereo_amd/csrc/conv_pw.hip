@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
   constexpr int WLD = (FSMI_NPROD == 3 ? 4 : 2) * TM + FSMI_PW_WLD_ADJ;
   auto load_wf = [&](auto buf_c, int c) FSMI_HALO_INL {
     constexpr int buf = decltype(buf_c)::value;
-    const size_t base = static_cast<size_t>(c) * a.CoutP * HKC;
+    const size_t base = weight_base<false, 1>(a, nck, c, 0);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -134,20 +134,14 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   bool pix_ok[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) pix_ok[j] = px0 + (wn * TN + j) * 32 + rl < HW;
 
   float scale = 1.f;
-  int sx = kNoExp;
-  bool ovf = false;
+  BlockExp<2> bx;
   // chunk q (buffer parity P): prefetch weights q+1, wait for chunk q and weights q (the
   // (NS-2)*OPS + WLD younger memory ops may stay in flight), barrier, refill the slot of chunk q-1
   // with chunk q+NS-1, MFMAs.  (A second barrier per chunk after the MFMAs, the round-2 schedule,
@@ -169,9 +163,8 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
     bar();
     dma(min(c + NS - 1, c_end - 1), (q + NS - 1) % NS);
     const float* xs = ring[q % NS];
-    // block exponent (range mode 2) from the first chunk holding a nonzero value (an all-zero first
-    // chunk would leave scale 1 and drop small later values to fp16 subnormals)
-    if (sx == kNoExp) {
+    // block exponent (range mode 2), from the fp32 ring slot
+    if (bx.wants_max()) {
       float m = 0.f;
 #pragma unroll
       for (int u = 0; u < CHF / 1024; ++u) {
@@ -180,12 +173,11 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
         const bool okc = c * HKC + row < a.Cin;
         m = fmaxf(m, okc ? fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))) : 0.f);
       }
-      m = wave_max(m);
-      if (lane == 0) red[wave] = m;
+      bx.publish(m, red, lane, wave);
       wait_lgkm0();
       bar();
-      sx = __builtin_amdgcn_readfirstlane(chunk_exp<kRangeHeadroom>(red4_max(red)));
-      scale = exp2i(sx == kNoExp ? 0 : sx);
+      bx.settle(acc, red);
+      scale = bx.scale();
     }
     if constexpr (COOP) {
       // the block's one split of chunk q: task = (8-channel group g, pixel), ring rows g*8 .. g*8+7
@@ -202,7 +194,7 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
           x[t] = (t < nvalid && pok) ? v * scale : 0.f;
           mx = fmaxf(mx, fabsf(x[t]));
         }
-        ovf |= mx >= 65504.f;
+        bx.ovf |= mx >= 65504.f;
         const half8 hi = __builtin_convertvector(x, half8);
         *reinterpret_cast<half8*>(&Xh[P][px][8 * gq]) = hi;
         if constexpr (FSMI_NPROD == 3)
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
           x[t] = (t < nvalid && pix_ok[j]) ? v * scale : 0.f;
           mx = fmaxf(mx, fabsf(x[t]));
         }
-        ovf |= mx >= 65504.f;
+        bx.ovf |= mx >= 65504.f;
         bh[j] = __builtin_convertvector(x, half8);
         if constexpr (FSMI_NPROD == 3) bl[j] = __builtin_convertvector(x - __builtin_convertvector(bh[j], f32x8), half8);
       }
@@ -264,9 +256,9 @@ __global__ __launch_bounds__(256) void conv_pw_kernel(HaloArgs a) {
     if (q < n) step(std::integral_constant<int, 0>(), std::true_type(), q);
   }
   wait_vmcnt<0>();                                 // the tail's clamped prefetches land before exit
-  flag_overflow(a, ovf);
+  flag_overflow(a, bx.ovf);
 
-  const float xinv = exp2i(sx == kNoExp ? 0 : -sx);
+  const float xinv = bx.inv();
   if (a.nsplit > 1) {                              // raw partials (packed units) into ws slot `split`
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
